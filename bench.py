@@ -12,7 +12,9 @@ clips resident in HBM, random-init weights.  One "step" = Trainer.train(): zero_
 psnd_stft_fwd launches, the separator under bf16 autocast, psnd_mel_fwd x2), NaN check, backward
 (incl. psnd_mel_bwd), flat-bucket RCCL all-reduce overlapped with backward, Adam step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement; `settle` = untimed set-up steps in front of the warm-up) with these extra objects:
+Prints ONE JSON line on rank 0 (`settle` = untimed set-up steps in front of the warm-up).  A plain run sets up, warms up, times the K
+steps and prints the headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  `--dump-outputs DIR` writes
+what the last timed step computed (bench_outputs).  `--full` adds these objects, each measured by runs of its own after the timed steps:
   roofline         the STFT kernel the timed step launches (psnd_stft_mag_nfk: wav -> magnitude (N, F, K), stft_fwd_n1024q_kernel) on a
                    544 MB working set (1024 clips, >> the 256 MiB Infinity Cache): algorithmic bytes 4*N*T + 4*N*K*F per launch / mean
                    launch duration (HIP events on the launch stream, measured in this run) against 8 TB/s; frac_config5 / frac_nkf /
@@ -32,6 +34,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement; `settle` = untim
   cpu_baseline_torch_stft  the same step with the reference's torch.stft front end (STFTTorchAudio) instead
   timing           ms/step of the contract region and of further identical K-step blocks (>= 100 ms timed in all): the spread
 `--config 3 | 4 | 5 --gpus N` runs BASELINE configs[2] / [3] / [4] data-parallel under the same contract (config_bench).
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full                     # every figure above
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs out_dir     # + the last timed step's outputs as .npy
 """
 import argparse
 import json
@@ -162,6 +167,7 @@ def build_step(device, amp, static=True, cpu_frontend='port', fused_loss=True, l
                 with torch.autocast('cuda', dtype=torch.bfloat16, enabled=amp):
                     loss, _ = self.model.spectral_l1_loss(mag_mix, mag_ref, mel_ref, fe._mel_plan(), N_MEL, 1.0, 0.5, 1e-6, fe.min_db,
                                                           fe.max_db, layout='nfk' if nfk else 'nkf')
+                self.last_loss = loss.detach()      # the value only (no autograd graph kept alive); captured: every replay rewrites it
                 return loss, {'loss': (loss, LogType.SCALAR)}
             if amp:
                 with torch.autocast('cuda', dtype=torch.bfloat16):
@@ -173,6 +179,7 @@ def build_step(device, amp, static=True, cpu_frontend='port', fused_loss=True, l
                 loss = l1sum([(est, mag_ref), (logmel_of_mag(est), mel_ref)], (1.0, 0.5))
             else:
                 loss = l1(est, mag_ref) + 0.5 * l1(logmel_of_mag(est), mel_ref)
+            self.last_loss = loss.detach()
             return loss, {'loss': (loss, LogType.SCALAR)}
 
     torch.manual_seed(1234)
@@ -180,10 +187,36 @@ def build_step(device, amp, static=True, cpu_frontend='port', fused_loss=True, l
     return StepTrainer, model
 
 
+DUMP_BYTES = 60 * 10 ** 6        # what --dump-outputs writes at most (data; the .npy headers stay well inside 64 MB)
+
+
+def _trainer_outputs(tr):
+    """what a training step hands its caller: the loss, the updated parameters and the gradients they were updated with"""
+    out = {'loss': tr.last_loss} if getattr(tr, 'last_loss', None) is not None else {}
+    for name, p in tr._bare_model.named_parameters():
+        out['param.' + name] = p
+        if p.grad is not None:
+            out['grad.' + name] = p.grad
+    return out
+
+
+def bench_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy in float32.  When they hold more than DUMP_BYTES in all, each is cut
+    to the same fraction of its elements, at flat positions drawn from a fixed seed (the same for every run with the same arguments)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    frac = min(1.0, DUMP_BYTES / max(total, 1))
+    for name, t in arrays.items():
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        if frac < 1.0:
+            k = max(1, int(a.size * frac))
+            a = a[np.unique(np.random.default_rng(0).integers(0, a.size, k))]
+        np.save(os.path.join(path, name + '.npy'), a.reshape(t.shape) if frac == 1.0 else a)
+
+
 def gpu_bench(args):
     from pytorch_sound_amd import distributed as pdist
     from pytorch_sound_amd import kernels as K
-    from pytorch_sound_amd._lib import lib, ptr, stream_ptr, check
     if args.force_ddp and int(os.environ.get('WORLD_SIZE', '1')) <= 1:
         # one-rank RCCL process group: the whole data-parallel step (flat buckets, captured all-reduce, hand-over from inside the
         # backward) on one GPU - what the reducer costs without a second device (the sum over one rank is the identity)
@@ -242,8 +275,9 @@ def gpu_bench(args):
         tr.step = step
         tr.train(step)
     barrier()
-    K.STFT_FWD_EVENTS = []
-    K.STFT_NFK_EVENTS = []
+    if args.full:                       # HIP events around the step's STFT launch, for roofline_instep
+        K.STFT_FWD_EVENTS = []
+        K.STFT_NFK_EVENTS = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step += 1
@@ -258,6 +292,43 @@ def gpu_bench(args):
         tdt = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tdt.item())
+    if args.dump_outputs and rank == 0:
+        bench_outputs(args.dump_outputs, _trainer_outputs(tr))
+    out = None
+    if rank == 0:
+        audio_s = world * N * CLIP_SECONDS * args.steps
+        out = {
+            'metric': 'audio-sec/s STFT+mel+fwd/bwd', 'value': audio_s / dt, 'unit': 'audio-s/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'settle': args.settle, 'ms_per_step': dt / args.steps * 1e3,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
+            'config': {'workload': 'configs[1]: Conv1d separator (4 x ResBlock1, C=256, on 513-bin magnitude), '
+                                   '22.05 kHz, STFT 1024/256, 80 mel, batch 32 x 2 s per GPU, Adam, bf16 autocast',
+                       'global_batch': world * N, 'clip_seconds': CLIP_SECONDS, 'parallelism': 'dp%d' % world,
+                       'model_params': sum(p.numel() for p in model.parameters())},
+            'settle_note': '`settle` untimed set-up steps (clock ramp) run in front of the `warmup` steps; with --full, timing.blocks_ms_per_step shows what is left of the ramp',
+        }
+    if args.full:
+        extra = _full_figures(args, tr, device, distributed, rank, world, dt, step)
+        if out is not None:
+            out.update(extra)
+    return out, device
+
+
+def _full_figures(args, tr, device, distributed, rank, world, dt, step):
+    """--full: the figures beyond the headline, each from runs of its own behind the timed steps - the spread over further K-step blocks,
+    the step with its batches in pinned host memory, the STFT launch inside the timed steps, and on rank 0 the rooflines and the
+    single-GPU legs.  Every rank takes part (the blocks are collective); rank 0 gets the line's extra entries, the others None."""
+    from pytorch_sound_amd import kernels as K
+    from pytorch_sound_amd._lib import lib, ptr, stream_ptr, check
+    T = int(SR * CLIP_SECONDS)
+    N = BATCH_PER_GPU
+
+    def barrier():
+        torch.cuda.synchronize()
+        if distributed:
+            torch.distributed.barrier()
+            torch.cuda.synchronize()
+
     instep_nfk = len(K.STFT_NFK_EVENTS) > 0
     ev_instep = K.STFT_NFK_EVENTS if instep_nfk else K.STFT_FWD_EVENTS
     K.STFT_FWD_EVENTS = None
@@ -394,22 +465,13 @@ def gpu_bench(args):
             legs['config3_step'] = _leg_subprocess('config3')
             legs['config4_step'] = _leg_subprocess('config4')
             legs['dropin_step'] = _leg_subprocess('dropin')
-        audio_s = world * N * CLIP_SECONDS * args.steps
         out = {
-            'metric': 'audio-sec/s STFT+mel+fwd/bwd', 'value': audio_s / dt, 'unit': 'audio-s/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'settle': args.settle, 'ms_per_step': dt / args.steps * 1e3,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
-            'config': {'workload': 'configs[1]: Conv1d separator (4 x ResBlock1, C=256, on 513-bin magnitude), '
-                                   '22.05 kHz, STFT 1024/256, 80 mel, batch 32 x 2 s per GPU, Adam, bf16 autocast',
-                       'global_batch': world * N, 'clip_seconds': CLIP_SECONDS, 'parallelism': 'dp%d' % world,
-                       'model_params': sum(p.numel() for p in model.parameters())},
-            'settle_note': '`settle` untimed set-up steps (clock ramp) run in front of the `warmup` steps; timing.blocks_ms_per_step shows what is left of the ramp',
             'roofline': roofline, 'roofline_instep': roofline_instep, 'roofline_nkf': roofline_nkf, 'roofline_config5': roofline_config5,
             'roofline_config5_nkf': roofline_config5_nkf, 'roofline_copy': roofline_copy, 'roofline_conv': roofline_conv,
             'roofline_mel': roofline_mel, 'h2d_inclusive': h2d, 'timing': timing,
         }
         out.update(legs)
-    return out, device
+    return out
 
 
 
@@ -477,6 +539,7 @@ def _config3_build(device):
                 y = self.model(m)
             y = y.float().squeeze(1)
             loss = K.l1_loss(mel(y), m)                 # F.l1_loss as psnd_l1_loss_fwd / _bwd (abs / mean / sign / scale: 5 library launches otherwise)
+            self.last_loss = loss.detach()
             return loss, {'loss': (loss, LogType.SCALAR)}
 
     g = torch.Generator().manual_seed(1 + int(os.environ.get('RANK', '0')))
@@ -529,6 +592,7 @@ def _config4_build(device, T=1292):
             with torch.autocast('cuda', dtype=torch.bfloat16):
                 y = self.model(mel_, pad)
             loss = K.masked_l1_loss(y.float(), mel_, valid)
+            self.last_loss = loss.detach()
             return loss, {'loss': (loss, LogType.SCALAR)}
 
     g = torch.Generator().manual_seed(2 + int(os.environ.get('RANK', '0')))
@@ -715,6 +779,8 @@ def config_bench(args):
         tdt = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tdt.item())
+    if args.dump_outputs and rank == 0:
+        bench_outputs(args.dump_outputs, {'mag': mag} if args.config == 5 else _trainer_outputs(tr))
     if rank != 0:
         return None
     red = getattr(tr, '_reducer', None) if args.config != 5 else None
@@ -1045,15 +1111,19 @@ def cpu_baseline(seconds, frontend='port'):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=30)
+    ap.add_argument('--steps', type=int, default=30, help='timed steps (ms_per_step = their time / steps)')
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: timing spread, host-memory batches, rooflines, config-3 / config-4 / drop-in legs, CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed (loss, parameters, gradients; config 5: magnitudes) as DIR/<name>.npy, float32')
     ap.add_argument('--pool', type=int, default=8, help='distinct synthetic batches resident in HBM')
     ap.add_argument('--settle', type=int, default=40, help='untimed set-up steps in front of the W warm-up steps (clock ramp)')
-    ap.add_argument('--cpu-seconds', type=float, default=20.0, help='CPU baseline budget (60 %% dense-DFT port, 40 %% torch.stft variant)')
+    ap.add_argument('--cpu-seconds', type=float, default=20.0, help='(--full) CPU baseline budget (60 %% dense-DFT port, 40 %% torch.stft variant)')
     ap.add_argument('--no-graph', action='store_true', help='enqueue every kernel of the step eagerly (no hipGraph replay)')
     ap.add_argument('--prefetch', action='store_true', help='stage the next batch (copy + feature extraction) on a side stream')
     ap.add_argument('--unfused-loss', action='store_true', help='the loss as separate nodes (mask head, mel, two L1 terms) instead of the fused one')
-    ap.add_argument('--no-legs', action='store_true', help='skip the bounded config-3 / config-4 step legs (config3_step, config4_step)')
+    ap.add_argument('--no-legs', action='store_true', help='(--full) skip the bounded config-3 / config-4 step legs (config3_step, config4_step)')
     ap.add_argument('--force-ddp', action='store_true', help='single GPU with a one-rank RCCL group: the data-parallel reducer path on one device')
     ap.add_argument('--no-handover', action='store_true', help='(with a reducer) gradients reach the buckets through autograd hooks only (round 3)')
     ap.add_argument('--overlap-prepare', action='store_true', help="the next batch's feature extraction behind this step's backward on a side stream (Trainer.overlap_prepare)")
@@ -1065,6 +1135,8 @@ def main():
                     help='which BASELINE configuration the contract line runs (1-based as in BASELINE.json configs: 2 = the headline, 3 = conv vocoder DDP, '
                          '4 = transformer block DDP, 5 = 4096-point STFT of 30-s clips); 3 / 4 / 5 take --gpus N under torch.distributed.run like the headline')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     # RCCL (this torch build's) writes a five-line version banner to STDOUT when the process exits - behind the JSON line - unless its log level is
     # set: rank 0's line must be the last thing on stdout (a caller that wants RCCL's messages sets NCCL_DEBUG itself)
     os.environ.setdefault('NCCL_DEBUG', 'NONE')
@@ -1095,7 +1167,7 @@ def main():
         return
     out, device = gpu_bench(args)
     if out is not None:
-        if args.gpus == 1 and args.cpu_seconds > 0:
+        if args.full and args.gpus == 1 and args.cpu_seconds > 0:
             out['cpu_baseline'] = cpu_baseline(args.cpu_seconds * 0.6, 'port')
             out['cpu_baseline_torch_stft'] = cpu_baseline(args.cpu_seconds * 0.4, 'torch_stft')
     _emit_line(out)

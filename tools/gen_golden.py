@@ -402,6 +402,33 @@ def gen_hifigan():
     np.savez_compressed(os.path.join(OUT, 'hifigan.npz'), **out)
 
 
+def seeded_state_dict(like, seed=12):
+    """weights for the keys and shapes of `like` from one numpy seed, keys in sorted order: weight_g ~ U(0.2, 0.8), everything else
+    ~ N(0, 0.05^2).  Same recipe as tests/test_modules_golden.py."""
+    rs = np.random.RandomState(seed)
+    out = {}
+    for k in sorted(like):
+        shape = tuple(like[k].shape)
+        a = 0.2 + 0.6 * rs.random_sample(shape) if k.endswith('weight_g') else 0.05 * rs.standard_normal(shape)
+        out[k] = torch.from_numpy(a.astype(np.float32))
+    return out
+
+
+def gen_hifigan_v2():
+    """hifi_gan_v2 loaded with a seeded state dict (seeded_state_dict) in the key layout of the shipped asset (hifigan.npz v2ckpt/keys -
+    the asset's weights are not shipped with the tests): the reference's waveform on the seeded mel of hifigan.npz v2ckpt/mel"""
+    from pytorch_sound.models import build_model
+    from pytorch_sound.models.vocoders import hifi_gan  # noqa: F401  (registers)
+    gen = build_model('hifi_gan_v2')
+    sd = seeded_state_dict(gen.state_dict())
+    assert sorted(sd) == list(np.load(os.path.join(OUT, 'hifigan.npz'))['v2ckpt/keys'])
+    gen.load_state_dict(sd)
+    mel = np.load(os.path.join(OUT, 'hifigan.npz'))['v2ckpt/mel']
+    with torch.no_grad():
+        y = gen(torch.from_numpy(mel))
+    np.savez_compressed(os.path.join(OUT, 'hifigan_v2.npz'), y=y.numpy())
+
+
 def gen_trainer():
     import pytorch_sound.trainer as rt
     from pytorch_sound.utils.commons import LOGGER
@@ -668,7 +695,7 @@ def gen_lstft():
 def main():
     os.makedirs(OUT, exist_ok=True)
     install_stubs()
-    which = sys.argv[1:] or ['stft', 'impulse', 'logmel', 'torch_stft', 'torch_stft_modules', 'modules', 'hifigan', 'trainer', 'sound', 'data', 'filters', 'lstft']
+    which = sys.argv[1:] or ['stft', 'impulse', 'logmel', 'torch_stft', 'torch_stft_modules', 'modules', 'hifigan', 'hifigan_v2', 'trainer', 'sound', 'data', 'filters', 'lstft']
     for w in which:
         print('generating', w, flush=True)
         globals()['gen_' + w]()

@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r06; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -- python $ROOT/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-legs > $OUT/bench_prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_bench -- python $ROOT/bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 --no-legs > $OUT/bench_prof.log 2>&1
 python $ROOT/tools/kstats.py /tmp/p_bench 40 $OUT/r06_bench_step_kernel_stats.txt > /dev/null
 python $ROOT/tools/step_timeline.py /tmp/p_bench 30 $OUT/r06_step_timeline.txt > /dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_c3 -- python $ROOT/bench.py --leg config3 > $OUT/c3.log 2>&1
