@@ -43,10 +43,17 @@ class _Node:
     shape = ()
     device = None
     requires_grad = False
-    _real = None
+    _real = None               # the real tensor, with its autograd history when the node requires a gradient
+    _plain = None              # a node that requires a gradient, formed without one: a use under no_grad, or the estimate the fused loss formed
 
     def real(self):
         if self._real is None:
+            if self.requires_grad and not torch.is_grad_enabled():
+                # a metric under no_grad: it must neither hand a history-less tensor to a later differentiable use nor keep the node from the
+                # fused loss (Sum._fused declines a materialised estimate)
+                if self._plain is None:
+                    self._plain = self._materialize()
+                return self._plain
             self._real = self._materialize()
         return self._real
 
@@ -168,7 +175,12 @@ class Sum(_Node):
                                                            m.mel_filter.shape[0], K.LOG_E, float(lm.eps), None, lm.lo, lm.hi, float(w1), float(w2))
             est_real = est_real.detach()
         loss.psnd_nan_flag = cl.LAST_LOSS_NAN_FLAG[0]      # isnan(loss), written by the launch that formed the loss (Trainer._nan_flag)
-        est._real = est_real                               # for logging / metrics: carries no gradient of its own (the loss node holds it)
+        # for logging / metrics: carries no gradient of its own (the loss node holds it) - so only uses without a gradient get it; a differentiable
+        # use of the estimate after the loss forms it again through cl.MaskHeadCL, with its history
+        if est.requires_grad:
+            est._plain = est_real
+        else:
+            est._real = est_real
         return loss
 
     def _materialize(self):

@@ -13,6 +13,7 @@ lines.  What is new sits behind that surface:
   without a GPU the batch is passed through unchanged so the loop is testable on CPU.
 """
 import abc
+import contextlib
 import enum
 import glob
 import os
@@ -121,6 +122,26 @@ def _independent_stream(tries: int = 6):
     return best
 
 
+def _host_rng_fingerprint():
+    """the complete state of the host-side generators a forward() can draw from without naming one: python `random`, numpy's legacy global
+    RandomState (key, position, gauss cache - the key alone changes once per 624 draws) and torch's default CPU generator"""
+    import random
+    st = np.random.get_state()
+    return (hash(random.getstate()), hash((st[1].tobytes(), st[2], st[3], st[4])), hash(torch.get_rng_state().numpy().tobytes()))
+
+
+class _GeneratorWatch(torch.overrides.TorchFunctionMode):
+    """active while a watched eager forward() runs: notes any torch function handed an explicit torch.Generator (its state is invisible to
+    _host_rng_fingerprint, and a replay would repeat what it drew)"""
+    used = False
+
+    def __torch_function__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if not self.used and (isinstance(kwargs.get('generator'), torch.Generator) or any(isinstance(a, torch.Generator) for a in args)):
+            self.used = True
+        return func(*args, **kwargs)
+
+
 def dist_backend_is_nccl() -> bool:
     return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_backend() == 'nccl'
 
@@ -210,13 +231,22 @@ class Trainer:
         opt = self.optimizer
         if not self.adopt_optimizer or type(opt) not in (torch.optim.Adam, torch.optim.AdamW) or 'step' in opt.__dict__:
             return                                    # (an LR scheduler patched the instance's step(): leave it alone)
+        from torch.optim import optimizer as topt
+        if (getattr(opt, '_optimizer_step_pre_hooks', None) or getattr(opt, '_optimizer_step_post_hooks', None)
+                or getattr(topt, '_global_optimizer_pre_hooks', None) or getattr(topt, '_global_optimizer_post_hooks', None)):
+            return                                    # step hooks are torch's step() protocol: keep torch's own step (and eager steps)
         from pytorch_sound_amd import optim as poptim
+        decoupled = set()
         for g in opt.param_groups:
             if (g.get('amsgrad') or g.get('maximize') or g.get('differentiable') or g.get('capturable')
                     or any(isinstance(g[k], torch.Tensor) for k in ('lr', 'eps', 'weight_decay')) or any(isinstance(b, torch.Tensor) for b in g['betas'])
                     or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in g['params'])):
                 return
-        opt.__class__ = poptim.AdamW if type(opt) is torch.optim.AdamW else poptim.Adam
+            # torch >= 2.6: Adam(decoupled_weight_decay=True) is AdamW's update under Adam's type (and AdamW sets the key itself)
+            decoupled.add(g.get('decoupled_weight_decay', type(opt) is torch.optim.AdamW))
+        if not decoupled <= {True, False} or len(decoupled) != 1:
+            return                                    # groups that disagree, or a value the kernel does not implement
+        opt.__class__ = poptim.AdamW if decoupled == {True} else poptim.Adam
         opt._plans = {}
         self._opt_adopted = True
         self._log('optimizer %s adopted: its steps run as one HIP launch (pytorch_sound_amd.optim)' % type(opt).__name__)
@@ -237,36 +267,55 @@ class Trainer:
         """override: returns (loss tensor, {name: (value, LogType)})"""
         raise NotImplementedError
 
-    def _forward_resolved(self, *inputs, is_logging: bool = False):
+    def _watch_host_state(self) -> bool:
+        """graph_steps = 'auto' and a step could still be captured: an eager forward() is watched for host-side decisions"""
+        return (self.graph_steps == 'auto' and self._graph_auto_ok is not False and getattr(self, '_reducer', None) is None
+                and self.async_nan_check and self.scheduler is None and getattr(self.optimizer, '_step_supports_amp_scaling', False)
+                and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing())
+
+    def _forward_resolved(self, *inputs, is_logging: bool = False, watch: bool = False):
         """self.forward(...) with deferred tensors resolved (deferred.py: a loss written with torch ops on a model's deferred estimate becomes
-        the fused loss node here; anything else in `meta` the plain tensor it stands for)"""
+        the fused loss node here; anything else in `meta` the plain tensor it stands for, formed without a gradient).  watch: an eager training
+        step under graph_steps = 'auto' - a forward() that makes host-side decisions switches graph capture off"""
         from pytorch_sound_amd.deferred import Deferred, resolve
-        watch = (self.graph_steps == 'auto' and self._graph_auto_ok is None and torch.cuda.is_available()
-                 and not torch.cuda.is_current_stream_capturing())
+        watch = watch and self._watch_host_state()
         if watch:
-            import random
-            before = (hash(random.getstate()), hash(np.random.get_state()[1].tobytes()), hash(torch.get_rng_state().numpy().tobytes()))
+            before, gens = _host_rng_fingerprint(), _GeneratorWatch()
             self.__dict__['_watch_forward'], self.__dict__['_step_read_in_forward'] = True, False
         try:
-            loss, meta = self.forward(*inputs, is_logging=is_logging)
+            with gens if watch else contextlib.nullcontext():
+                loss, meta = self.forward(*inputs, is_logging=is_logging)
         finally:
             if watch:
                 self.__dict__['_watch_forward'] = False
         if watch:
-            after = (hash(random.getstate()), hash(np.random.get_state()[1].tobytes()), hash(torch.get_rng_state().numpy().tobytes()))
-            why = ('forward() reads self.step' if self.__dict__.get('_step_read_in_forward') else
-                   'forward() draws host-side random numbers' if after != before else None)
+            # a read of self.step on a logging step (labelling a log line) counts only before the first capture: logging steps never replay
+            why = ('forward() draws host-side random numbers' if _host_rng_fingerprint() != before else
+                   'forward() draws from a torch.Generator' if gens.used else
+                   'forward() reads self.step' if self.__dict__.get('_step_read_in_forward') and (not is_logging or self._graph_auto_ok is None)
+                   else None)
             if why is not None:
-                self._graph_auto_ok = False
-                self._log("graph_steps = 'auto': %s - the steps stay eager (set graph_steps = True to capture anyway)" % why)
+                self._stay_eager(why)
         if isinstance(loss, Deferred):
             real = resolve(loss)
             if meta:
-                meta = {k: ((real if v[0] is loss else resolve(v[0])), *v[1:]) if isinstance(v, tuple) and v else v for k, v in meta.items()}
+                with torch.no_grad():                    # logged values: a deferred estimate the fused loss formed is reused, not formed again
+                    meta = {k: ((real if v[0] is loss else resolve(v[0])), *v[1:]) if isinstance(v, tuple) and v else v for k, v in meta.items()}
             loss = real
         elif meta and any(isinstance(v, tuple) and v and isinstance(v[0], Deferred) for v in meta.values()):
-            meta = {k: (resolve(v[0]), *v[1:]) if isinstance(v, tuple) and v else v for k, v in meta.items()}
+            with torch.no_grad():
+                meta = {k: (resolve(v[0]), *v[1:]) if isinstance(v, tuple) and v else v for k, v in meta.items()}
         return loss, meta
+
+    def _stay_eager(self, why: str):
+        """graph_steps = 'auto' after a forward() that made a host-side decision: no capture from now on, and graphs captured before it (the
+        decision showed on a logging step or on the warm-up of another input signature) are dropped"""
+        if any('graph' in v for v in getattr(self, '_graphs', {}).values()):
+            torch.cuda.synchronize()                     # no replay of them still in flight
+            why += ' (after a capture: the captured steps are dropped)'
+        self._graphs = {}
+        self._graph_auto_ok = False
+        self._log("graph_steps = 'auto': %s - the steps stay eager (set graph_steps = True to capture anyway)" % why)
 
     def prepare(self, *inputs):
         """Optional override (not in the reference): parameter-free preprocessing of a batch (feature extraction)
@@ -534,18 +583,22 @@ class Trainer:
     # free of host synchronisation.  Logging steps and the first `graph_warmup` steps of a signature run eagerly.
     #
     # graph_steps = 'auto' (default, round 6): capture when it is SAFE to - no gradient reducer (a data-parallel run opts in with True, all
-    # ranks alike), and during the eager warm-up steps forward() neither consumed host-side randomness (python `random`, numpy, torch's
-    # CPU generator) nor read `self.step`: a replayed step repeats the HOST-side decisions of the captured call, so a forward that draws
-    # a crop on the host or anneals a weight by the step count must keep running.  A capture that fails (a host synchronisation inside
-    # forward: `.item()`, a pageable copy) is logged once and the Trainer stays eager.  What cannot be detected: side effects of forward()
-    # on Python state (appending to a list every step) - such a Trainer sets graph_steps = False.  True: always capture (errors raise);
-    # False: never.
+    # ranks alike), and during the eager warm-up steps forward() neither consumed host-side randomness (python `random`, numpy's global
+    # RandomState - its whole state, gauss cache included -, torch's default CPU generator, any torch.Generator handed to a torch function)
+    # nor read `self.step`: a replayed step repeats the HOST-side decisions of the captured call, so a forward that draws a crop on the host
+    # or anneals a weight by the step count must keep running.  The eager steps after a capture (logging steps, the warm-up of a new input
+    # signature) are watched as well: randomness seen there drops the captured graphs and the Trainer stays eager from then on.  A capture
+    # that fails (a host synchronisation inside forward: `.item()`, a pageable copy) is logged once and the Trainer stays eager.  What cannot
+    # be detected: side effects of forward() on Python state (appending to a list every step) and draws from generator OBJECTS of python or
+    # numpy (`random.Random(...)`, `np.random.default_rng(...)`, a `np.random.RandomState` instance) - such a Trainer sets
+    # graph_steps = False.  True: always capture (errors raise); False: never.
     graph_steps = 'auto'
     graph_warmup = 3
     _graph_auto_ok = None          # 'auto': None undecided / True / False (stay eager)
     # Trainer adopts a stock `torch.optim.Adam` / `AdamW` handed to it (exact types, amsgrad / maximize / capturable off, fp32 HIP
-    # parameters): the instance keeps its identity, param_groups and state, its class becomes pytorch_sound_amd.optim.Adam / AdamW - one
-    # launch per step, on-device NaN skip, capturable steps (trainer.py:215-216 calls whatever optimizer the recipe built).
+    # parameters, no step hooks of its own or global ones): the instance keeps its identity, param_groups and state, its class becomes
+    # pytorch_sound_amd.optim.Adam / AdamW (AdamW also for an Adam with decoupled_weight_decay=True) - one launch per step, on-device NaN
+    # skip, capturable steps (trainer.py:215-216 calls whatever optimizer the recipe built).
     adopt_optimizer = True
     _opt_adopted = None
     # (not in the reference) a prepare() that writes its outputs into persistent buffers of its own and returns those same
@@ -796,7 +849,7 @@ class Trainer:
             self._reducer.zero_grad()
         else:
             self.optimizer.zero_grad()
-        loss, meta = self._forward_resolved(*batch, is_logging=log_flag)
+        loss, meta = self._forward_resolved(*batch, is_logging=log_flag, watch=True)
 
         if self._can_skip_on_device(loss):
             self._train_device_skip(step, loss)

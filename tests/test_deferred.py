@@ -122,3 +122,47 @@ def test_custom_autograd_functions_get_the_real_tensor():
     y.sum().backward()
     want = torch.autograd.grad((torch.sigmoid(logits) * mag * 2).sum(), logits)[0]
     assert torch.allclose(logits.grad, want)
+
+
+@pytest.mark.parametrize('when', ['before_the_loss', 'before_it_resolves'])
+def test_a_metric_under_no_grad_leaves_the_loss_its_gradient(when):
+    """a metric on the estimate taken under torch.no_grad() - before the recipe is written, or after it is recorded but before it resolves -
+    must not hand the loss a history-less estimate: same loss and d(loss)/d(logits) as the recipe on plain tensors"""
+    fe, logits, mag, mag_ref, mel_ref = _setup()
+    ref = torch.sigmoid(logits) * mag
+    want = _recipe(fe, ref, mag_ref, mel_ref)
+    want.backward()
+    gw = logits.grad.clone()
+    with torch.no_grad():
+        metric_want = (ref - mag_ref).pow(2).mean()
+    logits.grad = None
+    node = _HostEst(logits, mag)
+    e = D.Deferred(node)
+    if when == 'before_the_loss':
+        with torch.no_grad():
+            metric = (e - mag_ref).pow(2).mean()
+        loss = _recipe(fe, e, mag_ref, mel_ref)
+    else:
+        loss = _recipe(fe, e, mag_ref, mel_ref)
+        with torch.no_grad():
+            metric = (e - mag_ref).pow(2).mean()
+    assert torch.allclose(metric, metric_want, rtol=1e-6, atol=1e-7) and not metric.requires_grad
+    real = D.resolve(loss)
+    assert real.requires_grad and real.grad_fn is not None
+    real.backward()
+    assert torch.allclose(real, want, rtol=1e-6, atol=1e-7)
+    assert torch.allclose(logits.grad, gw, rtol=1e-5, atol=1e-7)
+    with torch.no_grad():
+        again = (e - mag_ref).pow(2).mean()                     # a second no-grad use: the estimate is not formed once more
+    assert torch.equal(again, metric) and node.count == 2
+
+
+def test_a_differentiable_use_after_a_no_grad_one_has_its_gradient():
+    fe, logits, mag, mag_ref, _ = _setup()
+    ref = torch.sigmoid(logits) * mag
+    gw = torch.autograd.grad(F.mse_loss(ref, mag_ref), logits)[0]
+    e = D.Deferred(_HostEst(logits, mag))
+    with torch.no_grad():
+        D.resolve(e)
+    g = torch.autograd.grad(F.mse_loss(e, mag_ref), logits)[0]
+    assert torch.allclose(g, gw, rtol=1e-6, atol=1e-9)

@@ -21,7 +21,7 @@ def _setup(N=3, T=6000):
     return fe, model, noisy, clean
 
 
-def _step(fe, model, noisy, clean):
+def _step(fe, model, noisy, clean, between=None):
     with torch.no_grad():
         mag_ref, _ = fe.stft.transform(clean)
         mel_ref = fe(clean)
@@ -29,6 +29,8 @@ def _step(fe, model, noisy, clean):
     with torch.autocast('cuda', dtype=torch.bfloat16):
         est = model(mag_mix)
     est = est.float()
+    if between is not None:                                  # a use of the estimate before the loss is written (a metric)
+        between(est, mag_ref)
     mel_est = torch.log(torch.matmul(fe.mel_filter, est) + 1e-6).clamp(fe.min_db, fe.max_db)
     loss = F.l1_loss(est, mag_ref) + 0.5 * F.l1_loss(mel_est, mel_ref)
     return loss, est
@@ -182,3 +184,106 @@ def test_dropin_recipe_runs_bin_fastest_end_to_end():
     assert worst <= 2e-3, worst
     e = D.resolve(est)
     assert e.shape == (noisy.shape[0], 513, est.shape[2]) and torch.isfinite(e).all()
+
+
+def _plain_grads(fe, model, noisy, clean, extra=None):
+    """the recipe on plain tensors (deferred.ENABLED = False): loss [+ extra(est, mag_ref)] and every parameter gradient"""
+    from pytorch_sound_amd import deferred as D
+    D.ENABLED = False
+    try:
+        loss0, est0 = _step(fe, model, noisy, clean)
+        assert not isinstance(loss0, D.Deferred)
+        total = loss0
+        if extra is not None:
+            with torch.no_grad():
+                mag_ref0, _ = fe.stft.transform(clean)
+            total = loss0 + extra(est0, mag_ref0)
+        total.backward()
+        g0 = {n: p.grad.clone() for n, p in model.named_parameters()}
+        model.zero_grad(set_to_none=True)
+    finally:
+        D.ENABLED = True
+    return float(loss0.detach()), est0.detach(), g0
+
+
+def _worst(model, g0):
+    return max(float((p.grad - g0[n]).norm() / g0[n].norm().clamp_min(1e-20)) for n, p in model.named_parameters())
+
+
+def test_a_no_grad_metric_before_the_recipe_keeps_the_fused_loss():
+    """(a) a metric of the estimate under torch.no_grad() ahead of the loss: the loss still resolves to the fused node, with the plain ops'
+    value and parameter gradients"""
+    from pytorch_sound_amd import deferred as D
+    fe, model, noisy, clean = _setup()
+    l0, est0, g0 = _plain_grads(fe, model, noisy, clean)
+    metric = []
+
+    def snr(est, mag_ref):
+        with torch.no_grad():
+            metric.append(10 * torch.log10(mag_ref.pow(2).sum() / (est - mag_ref).pow(2).sum()))
+
+    loss, est = _step(fe, model, noisy, clean, between=snr)
+    real = D.resolve(loss)
+    assert real.grad_fn is not None and 'MaskHeadSpectralL1' in type(real.grad_fn).__name__
+    real.backward()
+    assert abs(float(real.detach()) - l0) <= 2e-6 * abs(l0)
+    worst = _worst(model, g0)
+    assert worst <= 2e-3, worst
+    with torch.no_grad():
+        mag_ref0, _ = fe.stft.transform(clean)
+        want = 10 * torch.log10(D.resolve(mag_ref0).pow(2).sum() / (est0 - D.resolve(mag_ref0)).pow(2).sum())
+    assert abs(float(metric[0]) - float(want)) <= 1e-3 * abs(float(want)) + 1e-3
+
+
+def test_a_differentiable_use_after_the_fused_loss_has_its_gradient():
+    """(b) the fused loss resolved, then `loss + F.mse_loss(est, mag_ref)`: the mse term must reach the parameters (the estimate the fused
+    node left behind is detached - a differentiable use forms it again with its history)"""
+    from pytorch_sound_amd import deferred as D
+    fe, model, noisy, clean = _setup()
+    mse = lambda est, mag_ref: F.mse_loss(est, mag_ref)                    # noqa: E731
+    l0, _, g0 = _plain_grads(fe, model, noisy, clean, extra=mse)
+    loss, est = _step(fe, model, noisy, clean)
+    real = D.resolve(loss)
+    assert 'MaskHeadSpectralL1' in type(real.grad_fn).__name__
+    with torch.no_grad():
+        mag_ref, _ = fe.stft.transform(clean)
+    total = real + F.mse_loss(est, mag_ref)
+    total.backward()
+    assert abs(float(real.detach()) - l0) <= 2e-6 * abs(l0)
+    worst = _worst(model, g0)
+    assert worst <= 2e-3, worst
+
+
+def test_estimate_logged_in_meta_is_the_fused_one():
+    """(c) the estimate handed to the Trainer's `meta` on a logging step: the logged tensor is the estimate the fused loss formed (no second
+    mask-head launch, no gradient), and the loss is still the fused node with the plain ops' gradients"""
+    import tempfile
+    from pytorch_sound_amd import deferred as D
+    from pytorch_sound_amd.trainer import Trainer, LogType
+    fe, model, noisy, clean = _setup()
+    l0, est0, g0 = _plain_grads(fe, model, noisy, clean)
+
+    class Step(Trainer):
+        def forward(self, noisy, clean, is_logging=False):
+            loss, est = _step(fe, self.model, noisy, clean)
+            self.last_est = est
+            meta = {'loss': (loss, LogType.SCALAR)}
+            if is_logging:
+                meta['est'] = (est, LogType.AUDIO)
+            return loss, meta
+
+    pool = [(noisy, clean)]
+    tr = Step(model, torch.optim.Adam(model.parameters(), lr=1e-3), pool, pool, max_step=1, valid_max_step=1, save_interval=10 ** 9,
+              log_interval=1, save_dir=tempfile.mkdtemp(prefix='psnd_def_'), seed=1)
+    model.zero_grad(set_to_none=True)
+    loss, meta = tr._forward_resolved(noisy, clean, is_logging=True)
+    assert 'MaskHeadSpectralL1' in type(loss.grad_fn).__name__ and meta['loss'][0] is loss
+    logged = meta['est'][0]
+    with torch.no_grad():
+        again = D.resolve(tr.last_est)
+    assert not isinstance(logged, D.Deferred) and not logged.requires_grad and logged is again
+    assert float((logged - est0).norm() / est0.norm()) <= 2e-3
+    loss.backward()
+    assert abs(float(loss.detach()) - l0) <= 2e-6 * abs(l0)
+    worst = _worst(model, g0)
+    assert worst <= 2e-3, worst
