@@ -589,6 +589,38 @@ int psnd_pqmf_analysis(const float *x, const float *filt, int64_t B, int64_t T, 
 int psnd_pqmf_synthesis(const float *x, const float *filt, int64_t B, int64_t M, int64_t T_out, int subbands, int taps, int flip,
                         float scale, float *y, void *stream);
 
+/* ---- LearnableSTFT (models/transforms.py:104-203): the trainable analysis / synthesis filterbank, exact fp32 (v_mfma_f32_32x32x2_f32) -------
+ *  The reference runs F.conv1d / F.conv_transpose1d of the (C, 1, n) basis times the window with stride hop.  Here the frames are a
+ *  strided view of the waveform (tap stride 1, frame stride hop): no unfolded (N, n, F) tensor exists.  basis (C, n), window (n) fp32; the
+ *  product basis[c][m] * window[m] is rounded to fp32 before it is multiplied, as the reference's `basis * fft_window` is.
+ *  psnd_lstft_analysis: spec[z][c][f] = sum_m basis[c][m] window[m] x[z][f hop + m];  x (N, Lx) already padded, F = (Lx - n) / hop + 1,
+ *      spec (N, C, F).  mag, phase (N, C / 2, F), both or neither (NULL): mag = sqrt(re^2 + im^2), phase = atan2(im, re) with re = rows
+ *      [0, C / 2) and im = rows [C / 2, C) of spec (the reference's chunk(2, 1)), one element pass behind the product; C even then.
+ *      transform (:165-178), and the input gradient of inverse (basis = inverse_basis).
+ *  psnd_lstft_mag_bwd: gspec (N, C, F) = [gmag re / mag ; gmag im / mag] from spec, mag, gmag (N, C / 2, F).  A bin with mag == 0 gives
+ *      (gmag / 0) * 0 = NaN, as autograd of sqrt does and psnd_stft_bwd does.
+ *  psnd_lstft_synthesis: y[z][s] = mult[s] * sum_c sum_f g[z][c][f] basis[c][s - f hop] window[s - f hop]  (0 <= s - f hop < n);
+ *      = conv_transpose1d(g, (basis * window)[:, None, :], stride=hop).  g (N, C, F), y (N, Ly) with Ly >= n + hop (F - 1); samples
+ *      behind the last frame are written as zeros.  mult (Ly) or NULL: a per-sample factor applied in the epilogue (inverse's envelope
+ *      division and n / hop scale, :180-203).  Gather (polyphase) form, s = q hop + r: the reduction runs over (j, c) with tap j hop + r
+ *      and frame q - j, phases r along the rows and hop blocks q of all clips along the columns of the product - every sample is written
+ *      once: no atomics, no zero-fill launch, the same bits from run to run.  hop need not divide n.
+ *      inverse, and the waveform gradient of transform (basis = forward_basis).
+ *  psnd_lstft_basis_grad: gb[c][m] = window[m] * sum_{z, f} g[z][c][f] x[z][f hop + m];  g (N, C, F), x (N, Lx), F <= (Lx - n) / hop + 1,
+ *      gb (C, n).  Partial sums over clip chunks x frame parts go into S = psnd_lstft_wgrad_slabs(N, C, n, F) slabs gb_part
+ *      (S * C * n floats, caller's) that are added in a fixed order: bit-reproducible.  forward_basis: g = the gradient of spec, x = the
+ *      padded waveform; inverse_basis: g = the spectrum inverse synthesised from, x = the gradient of the full-length y (Lx = n + hop (F - 1)).
+ *  PSND_E_ARG without touching the device: hop <= 0, n < 2, rows shorter than n, a NULL required pointer, odd C with mag / phase;
+ *  PSND_E_UNSUPPORTED: index ranges the 32-bit tile arithmetic does not cover. */
+int psnd_lstft_analysis(const float *x, const float *basis, const float *window, int64_t N, int64_t Lx, int C, int n, int hop, float *spec,
+                        float *mag, float *phase, void *stream);
+int psnd_lstft_mag_bwd(const float *spec, const float *mag, const float *gmag, int64_t N, int C, int64_t F, float *gspec, void *stream);
+int psnd_lstft_synthesis(const float *g, const float *basis, const float *window, const float *mult, int64_t N, int C, int64_t F, int n,
+                         int hop, int64_t Ly, float *y, void *stream);
+int64_t psnd_lstft_wgrad_slabs(int64_t N, int C, int n, int64_t F);
+int psnd_lstft_basis_grad(const float *g, const float *x, const float *window, int64_t N, int64_t Lx, int C, int n, int hop, int64_t F,
+                          float *gb_part, float *gb, void *stream);
+
 /* ---- F.l1_loss (reduction 'mean') as used by the training recipes' spectral losses --------------------------------
  *  psnd_l1_loss_fwd: out[0] = mean |a - b| over n fp32 elements; part: psnd_l1_loss_blocks(n) doubles of scratch (one partial
  *      per 16384-element chunk, summed in a fixed order by a second tiny launch: bit-reproducible).

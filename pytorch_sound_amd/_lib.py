@@ -136,6 +136,11 @@ SIGNATURES = {
     'psnd_mask_head_bwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
     'psnd_pqmf_analysis': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _INT, _F, _P, _P]),
     'psnd_pqmf_synthesis': (_INT, [_P, _P, _I64, _I64, _I64, _INT, _INT, _INT, _F, _P, _P]),
+    'psnd_lstft_analysis': (_INT, [_P, _P, _P, _I64, _I64, _INT, _INT, _INT, _P, _P, _P, _P]),
+    'psnd_lstft_mag_bwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _P, _P]),
+    'psnd_lstft_synthesis': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _INT, _INT, _I64, _P, _P]),
+    'psnd_lstft_wgrad_slabs': (_I64, [_I64, _INT, _INT, _I64]),
+    'psnd_lstft_basis_grad': (_INT, [_P, _P, _P, _I64, _I64, _INT, _INT, _INT, _I64, _P, _P, _P]),
     'psnd_l1_loss_blocks': (_I64, [_I64]),
     'psnd_l1_loss_fwd': (_INT, [_P, _P, _I64, _P, _P, _P]),
     'psnd_l1_loss_bwd': (_INT, [_P, _P, _I64, _P, _P, _P, _P]),

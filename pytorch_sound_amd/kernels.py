@@ -1133,3 +1133,129 @@ def l1_loss_sum(pairs, weights):
 def l1_loss(input, target):
     """drop-in for torch.nn.functional.l1_loss(input, target) (reduction 'mean') on fp32 HIP tensors"""
     return L1Loss.apply(input, target)
+
+
+# ---------------------------------------------------------------------------------------------
+# LearnableSTFT (models/transforms.py:104-203): analysis / synthesis with trainable bases (psnd_lstft_*)
+# ---------------------------------------------------------------------------------------------
+def _lstft_basis(basis, window):
+    b = basis.reshape(basis.shape[0], basis.shape[-1])
+    _need_cuda(b, 'basis')
+    _need_cuda(window, 'window')
+    if window.numel() != b.shape[1]:
+        raise PsndError('lstft: a window of %d taps for a basis %s' % (window.numel(), tuple(basis.shape)))
+    return b.contiguous(), window.contiguous()
+
+
+def lstft_analysis(x, basis, window, hop, polar=False):
+    """spec[z][c][f] = sum_m basis[c][m] window[m] x[z][f hop + m] of a padded waveform x (N, Lx) - F.conv1d(x[:, None], (basis * window),
+    stride=hop) without frames in memory.  Returns spec (N, C, F), and with `polar` also mag, phase (N, C / 2, F)."""
+    _need_cuda(x, 'x')
+    b, w = _lstft_basis(basis, window)
+    x = x.contiguous()
+    (N, Lx), (C, n) = x.shape, b.shape
+    F = (Lx - n) // hop + 1 if hop > 0 and Lx >= n else 0
+    spec = torch.empty((N, C, max(F, 0)), dtype=torch.float32, device=x.device)
+    mag = torch.empty((N, C // 2, max(F, 0)), dtype=torch.float32, device=x.device) if polar else None
+    phase = torch.empty_like(mag) if polar else None
+    with torch.cuda.device(x.device):
+        check(lib().psnd_lstft_analysis(ptr(x), ptr(b), ptr(w), N, Lx, C, n, int(hop), ptr(spec), ptr(mag), ptr(phase), stream_ptr(x.device)),
+              'psnd_lstft_analysis')
+    return (spec, mag, phase) if polar else spec
+
+
+def lstft_synthesis(g, basis, window, hop, mult=None, length=None):
+    """y[z][s] = mult[s] * sum_{c, f} g[z][c][f] basis[c][s - f hop] window[s - f hop] - F.conv_transpose1d(g, (basis * window)[:, None],
+    stride=hop) in gather form (every sample written once).  g (N, C, F) -> y (N, length), length >= n + hop (F - 1) (default: equal)."""
+    _need_cuda(g, 'g')
+    b, w = _lstft_basis(basis, window)
+    g = g.contiguous()
+    (N, C, F), n = g.shape, b.shape[1]
+    if C != b.shape[0]:
+        raise PsndError('lstft_synthesis: %d rows for a basis %s' % (C, tuple(basis.shape)))
+    L = n + hop * (F - 1) if length is None else int(length)
+    if mult is not None:
+        _need_cuda(mult, 'mult')
+        if mult.numel() != L:
+            raise PsndError('lstft_synthesis: a multiplier of %d samples for rows of %d' % (mult.numel(), L))
+        mult = mult.contiguous()
+    y = torch.empty((N, L), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        check(lib().psnd_lstft_synthesis(ptr(g), ptr(b), ptr(w), ptr(mult), N, C, F, n, int(hop), L, ptr(y), stream_ptr(g.device)),
+              'psnd_lstft_synthesis')
+    return y
+
+
+def lstft_basis_grad(g, x, window, hop, like):
+    """gb[c][m] = window[m] * sum_{z, f} g[z][c][f] x[z][f hop + m] in the shape of `like` (the basis); slabs added in a fixed order"""
+    _need_cuda(g, 'g')
+    _need_cuda(x, 'x')
+    g, x, w = g.contiguous(), x.contiguous(), window.contiguous()
+    (N, C, F), Lx, n = g.shape, x.shape[1], w.numel()
+    slabs = int(lib().psnd_lstft_wgrad_slabs(N, C, n, F))
+    part = torch.empty((max(slabs, 1), C, n), dtype=torch.float32, device=g.device)
+    gb = torch.empty((C, n), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        check(lib().psnd_lstft_basis_grad(ptr(g), ptr(x), ptr(w), N, Lx, C, n, int(hop), F, ptr(part), ptr(gb), stream_ptr(g.device)),
+              'psnd_lstft_basis_grad')
+    return gb.view(like.shape)
+
+
+class LstftAnalysis(torch.autograd.Function):
+    """LearnableSTFT.transform behind the reflect padding: x (N, Lx) -> mag, phase (N, C / 2, F).  phase carries no gradient (the
+    reference takes it from `.data`).  Backward: gspec = gmag [re; im] / mag (NaN at a bin that is exactly zero, as autograd of sqrt and
+    STFT.transform's backward give), waveform gradient = the synthesis operator with the same basis, basis gradient = psnd_lstft_basis_grad;
+    either is skipped when it is not required."""
+
+    @staticmethod
+    def forward(ctx, x, basis, window, hop):
+        spec, mag, phase = lstft_analysis(x, basis, window, hop, polar=True)
+        ctx.save_for_backward(x, basis, window, spec, mag)
+        ctx.hop = hop
+        ctx.mark_non_differentiable(phase)
+        return mag, phase
+
+    @staticmethod
+    def backward(ctx, gmag, _gphase):
+        x, basis, window, spec, mag = ctx.saved_tensors
+        gx = gb = None
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        gmag = gmag.contiguous().float()
+        N, C, F = spec.shape
+        gspec = torch.empty_like(spec)
+        with torch.cuda.device(x.device):
+            check(lib().psnd_lstft_mag_bwd(ptr(spec), ptr(mag), ptr(gmag), N, C, F, ptr(gspec), stream_ptr(x.device)), 'psnd_lstft_mag_bwd')
+        if ctx.needs_input_grad[0]:
+            gx = lstft_synthesis(gspec, basis, window, ctx.hop, None, x.shape[1])
+        if ctx.needs_input_grad[1]:
+            gb = lstft_basis_grad(gspec, x, window, ctx.hop, basis)
+        return gx, gb, None, None
+
+
+class LstftSynthesis(torch.autograd.Function):
+    """LearnableSTFT.inverse between the polar -> (re, im) element ops and the final cut: spec (N, C, F) -> y (N, n + hop (F - 1)) times the
+    per-sample multiplier `mult` (envelope division and n / hop scale).  Backward: input gradient = the analysis operator with the same
+    basis on mult * gy, basis gradient = psnd_lstft_basis_grad with the roles of spectrum and waveform swapped."""
+
+    @staticmethod
+    def forward(ctx, spec, basis, window, mult, hop):
+        y = lstft_synthesis(spec, basis, window, hop, mult)
+        ctx.save_for_backward(spec, basis, window, mult)
+        ctx.hop = hop
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        spec, basis, window, mult = ctx.saved_tensors
+        gs = gb = None
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None, None
+        gy = gy.contiguous().float()
+        if mult is not None:
+            gy = gy * mult
+        if ctx.needs_input_grad[0]:
+            gs = lstft_analysis(gy, basis, window, ctx.hop)
+        if ctx.needs_input_grad[1]:
+            gb = lstft_basis_grad(spec, gy, window, ctx.hop, basis)
+        return gs, gb, None, None, None

@@ -7,6 +7,7 @@ STFT.inverse         STFT.inverse                           psnd_istft
 LogMelSpectrogram    LogMelSpectrogram.forward              psnd_stft_fwd + psnd_mel_fwd (+ bwd)
 STFTTorchAudio       forward -> (re, im); transform         psnd_stft_fwd(re,im) / psnd_stft_bwd
 Audio2Mel            forward (N,1,T) -> log10 mel           psnd_stft_fwd(HIFIGAN) + psnd_mel_fwd
+LearnableSTFT        transform / inverse (HIP tensors)      psnd_lstft_analysis / _synthesis / _basis_grad
 """
 from typing import Optional, Tuple
 
@@ -494,8 +495,12 @@ class PQMF(torch.nn.Module):
 class LearnableSTFT(nn.Module):
     """STFT whose analysis / synthesis bases are trainable (transforms.py:104-203, marked experimental there): the same dense
     [cos; -sin] bases as ``STFT`` but WITHOUT the window folded in (``fft_window`` is a buffer, multiplied in at every call), as
-    ``nn.Parameter``s when ``trainable_*``.  With trained bases the transform is no longer an FFT, so it runs as the strided
-    (transposed) convolution it is defined as - library kernels, not the FFT path."""
+    ``nn.Parameter``s when ``trainable_*``.  With trained bases the transform is no longer an FFT.  Host tensors run the reference's
+    strided (transposed) convolutions; a HIP tensor runs psnd_lstft_* (kernels.LstftAnalysis / LstftSynthesis): exact-fp32 matrix-core
+    contractions over a strided view of the padded waveform - no unfolded frames, no library convolution, bit-reproducible gradients,
+    capturable.  Other floating dtypes (and torch.autocast) are cast to that fp32 path and the result cast back; without libpsnd_hip.so a
+    HIP tensor raises.  The gradient of ``mag`` at a bin that is exactly zero is NaN (0 * inf), as autograd of the reference's sqrt gives
+    and as ``STFT.transform`` has it."""
 
     def __init__(self, filter_length: int = 1024, hop_length: int = 512, win_length: int = None, window: str = 'hann',
                  trainable_inverse: bool = True, trainable_forward: bool = True):
@@ -516,13 +521,48 @@ class LearnableSTFT(nn.Module):
             else:
                 self.register_buffer(name, t)
 
+    def _hip_mult(self, F: int, eps: float) -> torch.Tensor:
+        """n / hop / (envelope + eps) per sample of the full-length synthesis: the squared-window overlap-add envelope depends on (window,
+        hop, F) only - built once on the host and kept per F (the reference convolves ones with window^2 on every call)"""
+        w = self.fft_window
+        key = (F, float(eps), w.device, w.data_ptr(), w._version)
+        cache = self.__dict__.setdefault('_hip_mult_cache', {})
+        if key not in cache:
+            if len(cache) > 16:
+                cache.clear()
+            n, hop = self.filter_length, self.hop_length
+            w2 = w.detach().double().cpu().numpy() ** 2
+            env = np.zeros(n + hop * (F - 1))
+            for f in range(F):
+                env[f * hop:f * hop + n] += w2
+            with np.errstate(divide='ignore'):
+                cache[key] = torch.from_numpy((1.0 / (env + eps) * (n / hop)).astype(np.float32)).to(w.device)
+        return cache[key]
+
     def transform(self, wav: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if wav.is_cuda:
+            if wav.dim() != 2 or not wav.is_floating_point():
+                raise RuntimeError('LearnableSTFT.transform expects a floating-point (N, T) tensor, got %s %s' % (wav.dtype, tuple(wav.shape)))
+            with torch.autocast('cuda', enabled=False):
+                x = torch.nn.functional.pad(wav.float().unsqueeze(1), (self.pad_amount, self.pad_amount), mode='reflect').squeeze(1)
+                mag, phase = K.LstftAnalysis.apply(x, self.forward_basis.float(), self.fft_window.float(), self.hop_length)
+            return mag.to(wav.dtype), phase.to(wav.dtype)
         x = torch.nn.functional.pad(wav.unsqueeze(1), (self.pad_amount, self.pad_amount), mode='reflect')
         spec = torch.nn.functional.conv1d(x, self.forward_basis * self.fft_window, stride=self.hop_length)
         re, im = spec.chunk(2, 1)
         return torch.sqrt(re ** 2 + im ** 2), torch.atan2(im.data, re.data)
 
     def inverse(self, magnitude: torch.Tensor, phase: torch.Tensor, eps: float = 1e-9) -> torch.Tensor:
+        if magnitude.is_cuda:
+            if magnitude.dim() != 3 or magnitude.shape != phase.shape or not magnitude.is_floating_point():
+                raise RuntimeError('LearnableSTFT.inverse expects floating-point (N, K, F) magnitude and phase, got %s %s and %s'
+                                   % (magnitude.dtype, tuple(magnitude.shape), tuple(phase.shape)))
+            with torch.autocast('cuda', enabled=False):
+                m, ph = magnitude.float(), phase.float()
+                spec = torch.cat([m * torch.cos(ph), m * torch.sin(ph)], dim=1)
+                y = K.LstftSynthesis.apply(spec, self.inverse_basis.float(), self.fft_window.float(), self._hip_mult(spec.size(-1), eps),
+                                           self.hop_length)
+            return y[:, self.pad_amount:y.size(1) - self.pad_amount].to(magnitude.dtype)
         spec = torch.cat([magnitude * torch.cos(phase), magnitude * torch.sin(phase)], dim=1)
         y = torch.nn.functional.conv_transpose1d(spec, self.inverse_basis * self.fft_window, stride=self.hop_length)
         # squared-window overlap-add envelope, as STFT.inverse
