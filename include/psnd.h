@@ -454,6 +454,15 @@ int psnd_mha_bwd_parts(const float *kvq, const unsigned char *mask, const float 
  *      PSND_GN_WS_DOUBLES(C) doubles per sample): one pair of sums per row, written and then added up in a fixed order - no
  *      atomics, the statistics are the same bits from run to run (round 6; rounds 3-5 took 32 doubles per sample).
  *  psnd_groupnorm1_bwd: gx (gradient wrt x and wrt res), ggamma, gbeta (C) - all fully overwritten; ws as above.
+ *  psnd_groupnorm1_drop_fwd / _drop_bwd: the same with dropout in front of the sum, y = GroupNorm(1, C)(x * keep * scale + res) [relu]
+ *      (modules.py:54-58, :112-116), the mask never in memory: element i of the contiguous (N,C,T) x is kept iff word i % 4 of
+ *      Philox4x32-10(counter = {q lo, q hi, call lo, call hi} with q = i / 4, key = {seed lo, seed hi}) is >= thr; key : the {seed, call}
+ *      pair of this application in DEVICE memory (psnd_rng_next wrote it; the same pair for forward and backward), thr =
+ *      min(2^32 - 1, floor(p * 2^32)), scale = 1 / (1 - p).  A dropped element contributes exactly res.  _drop_bwd: gres = the gradient of
+ *      the sum (written when gres is not NULL: needs res and a buffer of its own), gx = gres * keep * scale (an exact zero where dropped).
+ *  psnd_rng_seed: state : two uint64 {seed, call} in device memory, overwritten by a one-thread kernel on the stream.
+ *  psnd_rng_next: key_out = state, then state.call += 1 - one thread, stream ordered and capturable: every replay of a hipGraph that holds
+ *      the launch advances the state, so every step draws fresh masks.
  *  psnd_softmax_keys_fwd: in place on scores (B,Tk,Tq): a = softmax over Tk of scale*s with key-padded rows at -inf,
  *      query-padded columns set to 0 (modules.py:66-76); mask (B,T) uint8, 1 = padded, or NULL.
  *  psnd_softmax_keys_bwd: gscores = scale * a * (gatt - sum_tk gatt*a). */
@@ -466,6 +475,14 @@ int psnd_groupnorm1_fwd(const float *x, const float *res, const float *gamma, co
 int psnd_groupnorm1_bwd(const float *gy, const float *x, const float *res, const float *gamma, const float *y,
                         const float *stats, int64_t N, int C, int64_t T, int relu, float *gx, float *ggamma,
                         float *gbeta, double *ws, void *stream);
+int psnd_groupnorm1_drop_fwd(const float *x, const float *res, const float *gamma, const float *beta, int64_t N, int C,
+                             int64_t T, float eps, int relu, float *y, float *stats, double *ws, const uint64_t *key,
+                             uint32_t thr, float scale, void *stream);
+int psnd_groupnorm1_drop_bwd(const float *gy, const float *x, const float *res, const float *gamma, const float *y,
+                             const float *stats, int64_t N, int C, int64_t T, int relu, float *gx, float *gres, float *ggamma,
+                             float *gbeta, double *ws, const uint64_t *key, uint32_t thr, float scale, void *stream);
+int psnd_rng_seed(uint64_t *state, uint64_t seed, uint64_t call, void *stream);
+int psnd_rng_next(uint64_t *state, uint64_t *key_out, void *stream);
 int psnd_softmax_keys_fwd(float *scores, const uint8_t *mask, int64_t B, int64_t T, float scale, void *stream);
 int psnd_softmax_keys_bwd(const float *att, const float *gatt, int64_t B, int64_t T, float scale, float *gscores,
                           void *stream);

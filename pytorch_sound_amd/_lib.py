@@ -19,6 +19,8 @@ _I64 = _c.c_int64
 _INT = _c.c_int
 _F = _c.c_float
 _D = _c.c_double
+_U32 = _c.c_uint32
+_U64 = _c.c_uint64
 
 # name -> (restype, argtypes); mirrors include/psnd.h one to one
 SIGNATURES = {
@@ -99,6 +101,10 @@ SIGNATURES = {
     'psnd_posenc': (_INT, [_P, _P, _F, _I64, _INT, _I64, _I64, _P, _P]),
     'psnd_groupnorm1_fwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _F, _INT, _P, _P, _P, _P]),
     'psnd_groupnorm1_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _I64, _INT, _I64, _INT, _P, _P, _P, _P, _P]),
+    'psnd_groupnorm1_drop_fwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _F, _INT, _P, _P, _P, _P, _U32, _F, _P]),
+    'psnd_groupnorm1_drop_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _I64, _INT, _I64, _INT, _P, _P, _P, _P, _P, _P, _U32, _F, _P]),
+    'psnd_rng_seed': (_INT, [_P, _U64, _U64, _P]),
+    'psnd_rng_next': (_INT, [_P, _P, _P]),
     'psnd_linear1x1_fwd': (_INT, [_P, _P, _P, _I64, _INT, _INT, _I64, _INT, _INT, _P, _P]),
     'psnd_linear1x1_wgrad_slabs': (_I64, [_I64, _INT, _INT, _I64]),
     'psnd_linear1x1_bwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _INT, _I64, _INT, _P, _P, _P, _P, _P]),

@@ -28,6 +28,55 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// dropout in front of the norm (modules.py:54-56, :112-114: drop_out(x) then layernorm(x + input)): s = x * keep * scale + res is formed
+// on load by the DROP instances of the four GroupNorm kernels below - no dropped copy and no mask tensor in memory.  keep is a pure
+// function of the element's linear index i in the contiguous (N, C, T) tensor and of the application's key {seed, call}:
+//   Philox4x32-10 with counter (q lo, q hi, call lo, call hi), q = i / 4, and key (seed lo, seed hi); the element's word is output word i % 4;
+//   kept iff word >= thr (thr = floor(p * 2^32), host side).  One Philox call serves four consecutive elements: a float4 of a row when
+//   T % 4 == 0, else the quads a row overlaps (a row then starts anywhere inside one).
+// The key is read through a device pointer (psnd_rng_next wrote it): a replayed hipGraph sees a fresh call number.
+// ------------------------------------------------------------------------------------------------------------
+struct GnDrop {
+    const uint64_t *key;     // {seed, call} of this application
+    uint32_t thr;
+    float scale;             // 1 / (1 - p)
+};
+
+__device__ __forceinline__ u32x4 philox4x32_10(uint64_t q, uint64_t call, uint64_t seed) {
+    uint32_t c0 = (uint32_t)q, c1 = (uint32_t)(q >> 32), c2 = (uint32_t)call, c3 = (uint32_t)(call >> 32);
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0, c1 = l1, c2 = h0 ^ c3 ^ k1, c3 = l0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return u32x4{c0, c1, c2, c3};
+}
+
+// s = x * keep * scale + res; a dropped element contributes exactly res (+0 without a residual)
+__device__ __forceinline__ float drop_sum(float x, float r, bool has_res, uint32_t w, const GnDrop &d) {
+    if (w < d.thr) return has_res ? r : 0.f;
+    return has_res ? __builtin_fmaf(x, d.scale, r) : x * d.scale;
+}
+
+// the elements of row [base, base + T) quad by quad: f(i, word of element i)
+template <class F>
+__device__ __forceinline__ void drop_row_scalar(size_t base, long long T, const GnDrop &d, F &&f) {
+    const uint64_t seed = d.key[0], call = d.key[1];
+    const size_t end = base + (size_t)T, q1 = (end - 1) >> 2;
+    for (size_t q = (base >> 2) + threadIdx.x; q <= q1; q += 256) {
+        const u32x4 w = philox4x32_10(q, call, seed);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t i = 4 * q + j;
+            if (i >= base && i < end) f(i, w[j]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // GroupNorm(1, C): one workgroup per (channel row chunk, sample); rows are contiguous T floats.
 // pass A: ws[n][c] = {sum, sum of squares} of s = x + res over the row (double: E[s^2] - mean^2 is formed in double).  One pair PER ROW,
 // written, not accumulated (round 6): no atomics, no memset launch in front, and every reader adds the C pairs of a sample up in the same
@@ -47,11 +96,31 @@ __device__ __forceinline__ void gn_ws_sum(const double *ws, const float *w, int 
     __syncthreads();
     a = (red[0] + red[1]) + (red[2] + red[3]), b = (red[4] + red[5]) + (red[6] + red[7]);
 }
-__global__ __launch_bounds__(256) void gn_stats_kernel(const float *x, const float *res, int C, long long T, double *ws) {
+template <bool DROP>
+__global__ __launch_bounds__(256) void gn_stats_kernel(const float *x, const float *res, int C, long long T, double *ws, GnDrop d) {
     const int c = blockIdx.x, n = blockIdx.y;
     const size_t base = ((size_t)n * C + c) * T;
     float s1 = 0.f, s2 = 0.f;
-    if (row_is_vec4(x + base, res ? res + base : nullptr, nullptr, T)) {           // 16-byte accesses (rows of T % 4 == 0 floats)
+    if constexpr (DROP) {
+        if (row_is_vec4(x + base, res ? res + base : nullptr, nullptr, T)) {           // T % 4 == 0: a float4 is one Philox quad
+            const uint64_t seed = d.key[0], call = d.key[1];
+            const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + base), *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr;
+            for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
+                const f32x4 v = x4[t], r = r4 ? r4[t] : f32x4{0.f, 0.f, 0.f, 0.f};
+                const u32x4 w = philox4x32_10((base >> 2) + t, call, seed);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float s = drop_sum(v[j], r[j], r4 != nullptr, w[j], d);
+                    s1 += s, s2 = __builtin_fmaf(s, s, s2);
+                }
+            }
+        } else {
+            drop_row_scalar(base, T, d, [&](size_t i, uint32_t w) {
+                const float s = drop_sum(x[i], res ? res[i] : 0.f, res != nullptr, w, d);
+                s1 += s, s2 = __builtin_fmaf(s, s, s2);
+            });
+        }
+    } else if (row_is_vec4(x + base, res ? res + base : nullptr, nullptr, T)) {           // 16-byte accesses (rows of T % 4 == 0 floats)
         const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + base), *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr;
         for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
             f32x4 v = x4[t];
@@ -77,9 +146,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *x, const flo
     }
 }
 
+template <bool DROP>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float *x, const float *res, const float *gamma, const float *beta,
                                                        int C, long long T, float eps, int relu, const double *ws, float *y,
-                                                       float *stats) {
+                                                       float *stats, GnDrop d) {
     const int c = blockIdx.x, n = blockIdx.y;
     const double M = (double)C * (double)T;
     double w1, w2;
@@ -91,6 +161,31 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *x, const flo
     if (c == 0 && threadIdx.x == 0) stats[2 * n] = mu, stats[2 * n + 1] = rstd;
     const float g = gamma[c] * rstd, b = beta[c] - mu * g;
     const size_t base = ((size_t)n * C + c) * T;
+    if constexpr (DROP) {
+        if (row_is_vec4(x + base, res ? res + base : nullptr, y + base, T)) {
+            const uint64_t seed = d.key[0], call = d.key[1];
+            const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + base), *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr;
+            f32x4 *y4 = reinterpret_cast<f32x4 *>(y + base);
+            for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
+                const f32x4 v = x4[t], r = r4 ? r4[t] : f32x4{0.f, 0.f, 0.f, 0.f};
+                const u32x4 w = philox4x32_10((base >> 2) + t, call, seed);
+                f32x4 o;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    o[j] = __builtin_fmaf(drop_sum(v[j], r[j], r4 != nullptr, w[j], d), g, b);
+                    if (relu) o[j] = fmaxf(o[j], 0.f);
+                }
+                y4[t] = o;
+            }
+            return;
+        }
+        drop_row_scalar(base, T, d, [&](size_t i, uint32_t w) {
+            float v = __builtin_fmaf(drop_sum(x[i], res ? res[i] : 0.f, res != nullptr, w, d), g, b);
+            if (relu) v = fmaxf(v, 0.f);
+            y[i] = v;
+        });
+        return;
+    }
     if (row_is_vec4(x + base, res ? res + base : nullptr, y + base, T)) {
         const f32x4 *x4 = reinterpret_cast<const f32x4 *>(x + base), *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr;
         f32x4 *y4 = reinterpret_cast<f32x4 *>(y + base);
@@ -118,14 +213,41 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *x, const flo
 // backward pass A: per row (n, c):  a = sum_t gy',  b = sum_t gy' * xhat   (gy' = gy * [y > 0] under ReLU)
 //   ws[n][c] = {a, b}  (written per row; pass B adds gamma[c] * {a, b} up per sample, and its workgroups of sample 0 add the rows of all
 //   samples up into gbeta[c] / ggamma[c] - no atomics, no zeroing launch: round 6)
+template <bool DROP>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float *gy, const float *x, const float *res, const float *gamma,
                                                             const float *y, const float *stats, int C, long long T, int relu,
-                                                            double *ws, float *ggamma, float *gbeta) {
+                                                            double *ws, float *ggamma, float *gbeta, GnDrop d) {
     const int c = blockIdx.x, n = blockIdx.y;
     const float mu = stats[2 * n], rstd = stats[2 * n + 1];
     const size_t base = ((size_t)n * C + c) * T;
     float a = 0.f, b = 0.f;
-    if (row_is_vec4(gy + base, x + base, res ? res + base : nullptr, T) && row_is_vec4(relu ? y + base : nullptr, nullptr, nullptr, T)) {
+    if constexpr (DROP) {
+        if (row_is_vec4(gy + base, x + base, res ? res + base : nullptr, T) && row_is_vec4(relu ? y + base : nullptr, nullptr, nullptr, T)) {
+            const uint64_t seed = d.key[0], call = d.key[1];
+            const f32x4 *g4 = reinterpret_cast<const f32x4 *>(gy + base), *x4 = reinterpret_cast<const f32x4 *>(x + base);
+            const f32x4 *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr, *y4 = relu ? reinterpret_cast<const f32x4 *>(y + base) : nullptr;
+            for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
+                f32x4 g = g4[t];
+                const f32x4 v = x4[t], r = r4 ? r4[t] : f32x4{0.f, 0.f, 0.f, 0.f};
+                if (y4) {
+                    const f32x4 yy = y4[t];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (!(yy[j] > 0.f)) g[j] = 0.f;
+                }
+                const u32x4 w = philox4x32_10((base >> 2) + t, call, seed);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a += g[j], b = __builtin_fmaf(g[j], (drop_sum(v[j], r[j], r4 != nullptr, w[j], d) - mu) * rstd, b);
+            }
+        } else {
+            drop_row_scalar(base, T, d, [&](size_t i, uint32_t w) {
+                float g = gy[i];
+                if (relu && !(y[i] > 0.f)) g = 0.f;
+                a += g;
+                b = __builtin_fmaf(g, (drop_sum(x[i], res ? res[i] : 0.f, res != nullptr, w, d) - mu) * rstd, b);
+            });
+        }
+    } else if (row_is_vec4(gy + base, x + base, res ? res + base : nullptr, T) && row_is_vec4(relu ? y + base : nullptr, nullptr, nullptr, T)) {
         const f32x4 *g4 = reinterpret_cast<const f32x4 *>(gy + base), *x4 = reinterpret_cast<const f32x4 *>(x + base);
         const f32x4 *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr, *y4 = relu ? reinterpret_cast<const f32x4 *>(y + base) : nullptr;
         for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
@@ -162,9 +284,12 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float *gy, con
 }
 
 // backward pass B: gx = rstd * (gamma gy' - S1/M - xhat * S2/M)
+// DROP: that is the gradient gs of s: gres = gs (written when gres is given), gx = gs * keep * scale - an exact zero where the element was dropped
+template <bool DROP>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float *gy, const float *x, const float *res, const float *gamma,
                                                            const float *y, const float *stats, int C, long long T, int relu,
-                                                           const double *ws, float *gx, int N, float *ggamma, float *gbeta) {
+                                                           const double *ws, float *gx, int N, float *ggamma, float *gbeta, float *gres,
+                                                           GnDrop d) {
     const int c = blockIdx.x, n = blockIdx.y;
     const double M = (double)C * (double)T;
     const float mu = stats[2 * n], rstd = stats[2 * n + 1];
@@ -182,6 +307,43 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float *gy, cons
     const float m1 = (float)(w1 / M), m2 = (float)(w2 / M);
     const float gc = gamma[c];
     const size_t base = ((size_t)n * C + c) * T;
+    if constexpr (DROP) {
+        if (row_is_vec4(gy + base, x + base, res ? res + base : nullptr, T) &&
+            row_is_vec4(relu ? y + base : nullptr, gx + base, gres ? gres + base : nullptr, T)) {
+            const uint64_t seed = d.key[0], call = d.key[1];
+            const f32x4 *g4 = reinterpret_cast<const f32x4 *>(gy + base), *x4 = reinterpret_cast<const f32x4 *>(x + base);
+            const f32x4 *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr, *y4 = relu ? reinterpret_cast<const f32x4 *>(y + base) : nullptr;
+            f32x4 *o4 = reinterpret_cast<f32x4 *>(gx + base), *q4 = gres ? reinterpret_cast<f32x4 *>(gres + base) : nullptr;
+            for (long long t = threadIdx.x; t < (T >> 2); t += 256) {
+                f32x4 g = g4[t], o, ox;
+                const f32x4 v = x4[t], r = r4 ? r4[t] : f32x4{0.f, 0.f, 0.f, 0.f};
+                if (y4) {
+                    const f32x4 yy = y4[t];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (!(yy[j] > 0.f)) g[j] = 0.f;
+                }
+                const u32x4 w = philox4x32_10((base >> 2) + t, call, seed);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    o[j] = rstd * (g[j] * gc - m1 - (drop_sum(v[j], r[j], r4 != nullptr, w[j], d) - mu) * rstd * m2);
+                    ox[j] = w[j] < d.thr ? 0.f : o[j] * d.scale;
+                }
+                o4[t] = ox;
+                if (q4) q4[t] = o;
+            }
+            return;
+        }
+        drop_row_scalar(base, T, d, [&](size_t i, uint32_t w) {
+            float g = gy[i];
+            if (relu && !(y[i] > 0.f)) g = 0.f;
+            const float xh = (drop_sum(x[i], res ? res[i] : 0.f, res != nullptr, w, d) - mu) * rstd;
+            const float o = rstd * (g * gc - m1 - xh * m2);
+            gx[i] = w < d.thr ? 0.f : o * d.scale;
+            if (gres) gres[i] = o;
+        });
+        return;
+    }
     if (row_is_vec4(gy + base, x + base, res ? res + base : nullptr, T) && row_is_vec4(relu ? y + base : nullptr, gx + base, nullptr, T)) {
         const f32x4 *g4 = reinterpret_cast<const f32x4 *>(gy + base), *x4 = reinterpret_cast<const f32x4 *>(x + base);
         const f32x4 *r4 = res ? reinterpret_cast<const f32x4 *>(res + base) : nullptr, *y4 = relu ? reinterpret_cast<const f32x4 *>(y + base) : nullptr;
@@ -407,7 +569,32 @@ __global__ __launch_bounds__(256) void softmax_keys_bwd4_kernel(const float *a, 
     }
 }
 
+// the dropout state of a device: {seed, call}.  psnd_rng_next hands the current pair to one dropout application and counts the call -
+// one thread, stream ordered, so a replayed hipGraph advances the state as the eager step does
+__global__ void rng_seed_kernel(uint64_t *state, uint64_t seed, uint64_t call) {
+    state[0] = seed, state[1] = call;
+}
+__global__ void rng_next_kernel(uint64_t *state, uint64_t *key_out) {
+    const uint64_t seed = state[0], call = state[1];
+    key_out[0] = seed, key_out[1] = call;
+    state[1] = call + 1;
+}
+
 }  // namespace
+
+extern "C" int psnd_rng_seed(uint64_t *state, uint64_t seed, uint64_t call, void *stream) {
+    if (!state) PSND_FAIL(PSND_E_ARG, "rng_seed: null pointer");
+    hipLaunchKernelGGL(rng_seed_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), state, seed, call);
+    PSND_CHECK_LAUNCH("rng_seed");
+    return PSND_OK;
+}
+
+extern "C" int psnd_rng_next(uint64_t *state, uint64_t *key_out, void *stream) {
+    if (!state || !key_out || state == key_out) PSND_FAIL(PSND_E_ARG, "rng_next: null or aliased pointer");
+    hipLaunchKernelGGL(rng_next_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), state, key_out);
+    PSND_CHECK_LAUNCH("rng_next");
+    return PSND_OK;
+}
 
 extern "C" int psnd_groupnorm1_fwd(const float *x, const float *res, const float *gamma, const float *beta, int64_t N, int C,
                                    int64_t T, float eps, int relu, float *y, float *stats, double *ws, void *stream) {
@@ -415,9 +602,25 @@ extern "C" int psnd_groupnorm1_fwd(const float *x, const float *res, const float
     if (N < 0 || C <= 0 || T <= 0 || N > 65535) PSND_FAIL(PSND_E_SHAPE, "groupnorm1_fwd: N=%lld C=%d T=%lld", (long long)N, C, (long long)T);
     if (N == 0) return PSND_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, C, (long long)T, ws);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, gamma, beta, C, (long long)T, eps, relu, ws, y, stats);
+    hipLaunchKernelGGL(gn_stats_kernel<false>, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, C, (long long)T, ws, GnDrop{});
+    hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, gamma, beta, C, (long long)T, eps, relu, ws, y, stats,
+                       GnDrop{});
     PSND_CHECK_LAUNCH("groupnorm1_fwd");
+    return PSND_OK;
+}
+
+extern "C" int psnd_groupnorm1_drop_fwd(const float *x, const float *res, const float *gamma, const float *beta, int64_t N, int C,
+                                        int64_t T, float eps, int relu, float *y, float *stats, double *ws, const uint64_t *key,
+                                        uint32_t thr, float scale, void *stream) {
+    if (!x || !gamma || !beta || !y || !stats || !ws || !key) PSND_FAIL(PSND_E_ARG, "groupnorm1_drop_fwd: null pointer");
+    if (N < 0 || C <= 0 || T <= 0 || N > 65535) PSND_FAIL(PSND_E_SHAPE, "groupnorm1_drop_fwd: N=%lld C=%d T=%lld", (long long)N, C, (long long)T);
+    if (!(scale >= 1.f) || !(scale <= 4294967296.f)) PSND_FAIL(PSND_E_ARG, "groupnorm1_drop_fwd: scale=%g is no 1 / (1 - p) of a rate in [0, 1)", scale);
+    if (N == 0) return PSND_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const GnDrop d{key, thr, scale};
+    hipLaunchKernelGGL(gn_stats_kernel<true>, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, C, (long long)T, ws, d);
+    hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(C, (unsigned)N), dim3(256), 0, s, x, res, gamma, beta, C, (long long)T, eps, relu, ws, y, stats, d);
+    PSND_CHECK_LAUNCH("groupnorm1_drop_fwd");
     return PSND_OK;
 }
 
@@ -428,11 +631,29 @@ extern "C" int psnd_groupnorm1_bwd(const float *gy, const float *x, const float 
     if (N < 0 || C <= 0 || T <= 0 || N > 65535) PSND_FAIL(PSND_E_SHAPE, "groupnorm1_bwd: bad shape");
     if (N == 0) return PSND_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws,
-                       ggamma, gbeta);
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws, gx, (int)N,
-                       ggamma, gbeta);
+    hipLaunchKernelGGL(gn_bwd_reduce_kernel<false>, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws,
+                       ggamma, gbeta, GnDrop{});
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws, gx,
+                       (int)N, ggamma, gbeta, static_cast<float *>(nullptr), GnDrop{});
     PSND_CHECK_LAUNCH("groupnorm1_bwd");
+    return PSND_OK;
+}
+
+extern "C" int psnd_groupnorm1_drop_bwd(const float *gy, const float *x, const float *res, const float *gamma, const float *y,
+                                        const float *stats, int64_t N, int C, int64_t T, int relu, float *gx, float *gres, float *ggamma,
+                                        float *gbeta, double *ws, const uint64_t *key, uint32_t thr, float scale, void *stream) {
+    if (!gy || !x || !gamma || !stats || !gx || !ggamma || !gbeta || !ws || !key || (relu && !y)) PSND_FAIL(PSND_E_ARG, "groupnorm1_drop_bwd: null pointer");
+    if (gres && (gres == gx || !res)) PSND_FAIL(PSND_E_ARG, "groupnorm1_drop_bwd: gres needs a residual and a buffer of its own");
+    if (N < 0 || C <= 0 || T <= 0 || N > 65535) PSND_FAIL(PSND_E_SHAPE, "groupnorm1_drop_bwd: bad shape");
+    if (!(scale >= 1.f) || !(scale <= 4294967296.f)) PSND_FAIL(PSND_E_ARG, "groupnorm1_drop_bwd: scale=%g is no 1 / (1 - p) of a rate in [0, 1)", scale);
+    if (N == 0) return PSND_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const GnDrop d{key, thr, scale};
+    hipLaunchKernelGGL(gn_bwd_reduce_kernel<true>, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws,
+                       ggamma, gbeta, d);
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(C, (unsigned)N), dim3(256), 0, s, gy, x, res, gamma, y, stats, C, (long long)T, relu, ws, gx,
+                       (int)N, ggamma, gbeta, gres, d);
+    PSND_CHECK_LAUNCH("groupnorm1_drop_bwd");
     return PSND_OK;
 }
 

@@ -476,11 +476,66 @@ class ReluLink:
         return m
 
 
+# dropout in front of the norm (modules.py:54-56, :112-114), formed inside the GroupNorm kernels: the mask is a pure function of the element's
+# index and of a {seed, call} pair (Philox4x32-10, include/psnd.h), the pair lives in DEVICE memory and every application takes it through
+# psnd_rng_next, which counts the call - stream ordered and capturable, so each replay of a step graph draws fresh masks.
+_DROPOUT_STATE = {}            # device index -> int64[2] device tensor holding the two uint64 {seed, call}
+_U64 = (1 << 64) - 1
+
+
+def _dropout_device(device):
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != 'cuda':
+        raise PsndError('the dropout state lives on a HIP device, got %s' % device)
+    return device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def dropout_seed(seed, call=0, device=None):
+    """(re)start the dropout stream of `device` at {seed, call}: a one-thread kernel on the current stream, no synchronisation"""
+    device = _dropout_device(device)
+    with torch.cuda.device(device):
+        st = _DROPOUT_STATE.get(device.index)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise PsndError('dropout on %s: no dropout state yet and a stream capture is under way (the state would live in the graph\'s '
+                                'memory) - call pytorch_sound_amd.kernels.dropout_seed(seed) before the capture' % device)
+            st = _DROPOUT_STATE[device.index] = torch.empty(2, dtype=torch.int64, device=device)
+        check(lib().psnd_rng_seed(ptr(st), int(seed) & _U64, int(call) & _U64, stream_ptr(device)), 'psnd_rng_seed')
+    return st
+
+
+def _dropout_state_tensor(device):
+    st = _DROPOUT_STATE.get(device.index)
+    # first use without seeding: torch.initial_seed() reads the default generator's seed and draws nothing from it
+    return st if st is not None else dropout_seed(torch.initial_seed(), 0, device)
+
+
+def dropout_state(device=None):
+    """(seed, call) of the next dropout application on `device` - SYNCHRONISES; for tests and checkpoints"""
+    seed, call = _dropout_state_tensor(_dropout_device(device)).cpu().tolist()
+    return seed & _U64, call & _U64
+
+
+def _dropout_reset(device=None):
+    """test hook: forget the state of `device`, as in a process that never used dropout"""
+    _DROPOUT_STATE.pop(_dropout_device(device).index, None)
+
+
+def dropout_threshold(p):
+    """(thr, scale) of rate p: an element is kept iff its Philox word is >= thr = min(2^32 - 1, floor(p * 2^32)); scale = 1 / (1 - p) in fp32"""
+    p = float(p)
+    if not 0.0 < p < 1.0 or np.float32(p) >= 1:
+        raise PsndError('dropout rate %r: the kernels take 0 < p < 1 (as an fp32 number)' % (p,))
+    return min(2 ** 32 - 1, int(math.floor(p * 2.0 ** 32))), float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
 class GroupNorm1(torch.autograd.Function):
-    """y = GroupNorm(1, C)(x + res) [-> ReLU]: statistics over (C x T) per sample (modules.py:58, :114-116)."""
+    """y = GroupNorm(1, C)(x + res) [-> ReLU]: statistics over (C x T) per sample (modules.py:58, :114-116).
+    drop = p: y = GroupNorm(1, C)(dropout_p(x) + res) [-> ReLU] in the same two launches (psnd_groupnorm1_drop_*), the mask recomputed
+    from the application's {seed, call} pair in every pass."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, relu, link=None):
+    def forward(ctx, x, res, gamma, beta, eps, relu, link=None, drop=None):
         _need_cuda(x, 'x')
         x = x.contiguous()
         res = None if res is None else res.contiguous()
@@ -490,29 +545,49 @@ class GroupNorm1(torch.autograd.Function):
         stats = torch.empty((N, 2), dtype=torch.float32, device=x.device)
         ws = torch.empty((N, 2 * C), dtype=torch.float64, device=x.device)         # PSND_GN_WS_DOUBLES(C) per sample: a pair of sums per row
         g32, b32 = gamma.detach().contiguous(), beta.detach().contiguous()
+        key = None
+        ctx.drop = None if drop is None else dropout_threshold(drop)
         with torch.cuda.device(x.device):
-            check(lib().psnd_groupnorm1_fwd(ptr(x), ptr(res), ptr(g32), ptr(b32), N, C, T, float(eps), int(relu), ptr(y),
-                                            ptr(stats), ptr(ws), stream_ptr(x.device)), 'psnd_groupnorm1_fwd')
+            if ctx.drop is None:
+                check(lib().psnd_groupnorm1_fwd(ptr(x), ptr(res), ptr(g32), ptr(b32), N, C, T, float(eps), int(relu), ptr(y),
+                                                ptr(stats), ptr(ws), stream_ptr(x.device)), 'psnd_groupnorm1_fwd')
+            else:
+                state = _dropout_state_tensor(x.device)
+                key = torch.empty(2, dtype=torch.int64, device=x.device)           # this application's {seed, call}: backward reads it again
+                check(lib().psnd_rng_next(ptr(state), ptr(key), stream_ptr(x.device)), 'psnd_rng_next')
+                check(lib().psnd_groupnorm1_drop_fwd(ptr(x), ptr(res), ptr(g32), ptr(b32), N, C, T, float(eps), int(relu), ptr(y),
+                                                     ptr(stats), ptr(ws), ptr(key), ctx.drop[0], ctx.drop[1], stream_ptr(x.device)),
+                      'psnd_groupnorm1_drop_fwd')
         ctx.relu, ctx.has_res = bool(relu), res is not None
-        ctx.save_for_backward(x, res, g32, y if relu else None, stats)
+        ctx.save_for_backward(x, res, g32, y if relu else None, stats, key)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, res, g32, y, stats = ctx.saved_tensors
+        x, res, g32, y, stats, key = ctx.saved_tensors
         gy = gy.contiguous()
         N, C, T = x.shape
         gx = torch.empty_like(x)
         gg = torch.empty(C, dtype=torch.float32, device=x.device)
         gb = torch.empty(C, dtype=torch.float32, device=x.device)
         ws = torch.empty((N, 2 * C), dtype=torch.float64, device=x.device)         # PSND_GN_WS_DOUBLES(C) per sample: a pair of sums per row
+        if ctx.drop is not None:
+            # two gradients: the sum's (the residual's) and, masked and scaled, x's; the residual's is written only when somebody takes it
+            gres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[1]) else None
+            with torch.cuda.device(x.device):
+                check(lib().psnd_groupnorm1_drop_bwd(ptr(gy), ptr(x), ptr(res), ptr(g32), ptr(y), ptr(stats), N, C, T, int(ctx.relu),
+                                                     ptr(gx), ptr(gres), ptr(gg), ptr(gb), ptr(ws), ptr(key), ctx.drop[0], ctx.drop[1],
+                                                     stream_ptr(x.device)), 'psnd_groupnorm1_drop_bwd')
+            if ctx.link is not None and gres is not None and ctx.link.offer(gres):
+                return gx, None, gg, gb, None, None, None, None
+            return gx, gres, gg, gb, None, None, None, None
         with torch.cuda.device(x.device):
             check(lib().psnd_groupnorm1_bwd(ptr(gy), ptr(x), ptr(res), ptr(g32), ptr(y), ptr(stats), N, C, T, int(ctx.relu),
                                             ptr(gx), ptr(gg), ptr(gb), ptr(ws), stream_ptr(x.device)), 'psnd_groupnorm1_bwd')
         if ctx.link is not None and ctx.needs_input_grad[1] and ctx.link.offer(gx):
             # the residual's gradient travels with the link: the first projection of the branch adds it in its input-gradient GEMM
-            return gx, None, gg, gb, None, None, None
-        return gx, (gx if ctx.has_res else None), gg, gb, None, None, None
+            return gx, None, gg, gb, None, None, None, None
+        return gx, (gx if ctx.has_res else None), gg, gb, None, None, None, None
 
 
 class SoftmaxKeys(torch.autograd.Function):

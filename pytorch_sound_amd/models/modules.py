@@ -35,16 +35,29 @@ def _to_kernel_dtype(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
-def _add_norm(norm: nn.GroupNorm, x: torch.Tensor, residual: torch.Tensor, relu: bool = False, link=None) -> torch.Tensor:
+def _add_norm(norm: nn.GroupNorm, x: torch.Tensor, residual: torch.Tensor, relu: bool = False, link=None, drop=None) -> torch.Tensor:
     """GroupNorm(1, C)(x + residual) [-> ReLU]; `link`: the kernels.ResidualLink the branch's first projection was given - the residual's
-    gradient then reaches the input through that projection's input-gradient GEMM instead of a separate accumulation pass"""
+    gradient then reaches the input through that projection's input-gradient GEMM instead of a separate accumulation pass; `drop`: the rate
+    of a dropout applied to x in front of the sum, inside the norm's kernels (HIP tensors only: `_drop_rate`)"""
     if _hip_ok(x):
         from pytorch_sound_amd import kernels as K
         if link is not None and residual.dtype != torch.float32:
             link = None                                      # (the gradient would be of the converted copy, not of `residual`)
-        return K.GroupNorm1.apply(x.float(), residual.float(), norm.weight.float(), norm.bias.float(), norm.eps, relu, link)
+        return K.GroupNorm1.apply(x.float(), residual.float(), norm.weight.float(), norm.bias.float(), norm.eps, relu, link, drop)
+    assert drop is None, 'the fused dropout is the HIP kernels\': a CPU tensor goes through nn.Dropout'
     y = norm(x + residual)
     return F.relu(y) if relu else y
+
+
+def _drop_rate(module: nn.Module, x: torch.Tensor):
+    """the dropout between a block's last projection and its norm (modules.py:54-56, :112-114) -> (x, rate for _add_norm).  On a HIP tensor
+    in training mode the norm's kernels apply it (psnd_groupnorm1_drop_*: no dropped copy, no mask tensor, no library kernel) and in eval mode
+    nothing is launched at all; CPU tensors keep nn.Dropout."""
+    if module.drop_out is None:
+        return x, None
+    if _hip_ok(x):
+        return x, (module.drop_out.p if module.training and module.drop_out.p > 0 else None)
+    return module.drop_out(x), None
 
 
 def _conv1x1(conv: nn.Conv1d, x: torch.Tensor, relu: bool = False, link=None, relu_link=None, hidden_out: bool = False, t_len=None,
@@ -129,9 +142,8 @@ class MultiHeadAttention(nn.Module):
             x, att = self.scale_dot_att(k, v, q, att_mask=mask)
             x = self._unfold_heads(x)
         x = _conv1x1(self.linear, x)
-        if self.drop_out is not None:
-            x = self.drop_out(x)
-        x = _add_norm(self.layernorm, x, input, link=link)
+        x, drop = _drop_rate(self, x)
+        x = _add_norm(self.layernorm, x, input, link=link, drop=drop)
         if in_dtype != x.dtype:
             x, att = x.to(in_dtype), (None if att is None else att.to(in_dtype))
         return x, att
@@ -190,9 +202,8 @@ class PointwiseFeedForward(nn.Module):
                 link = K.ResidualLink()
         x = _conv1x1(self.ff[2], _conv1x1(self.ff[0], input, relu=True, link=link, relu_link=relu_link, hidden_out=True, pad_rows=True),
                      relu_link=relu_link, t_len=input.size(-1))
-        if self.drop_out is not None:
-            x = self.drop_out(x)
-        x = _add_norm(self.layernorm, x, input, relu=True, link=link)
+        x, drop = _drop_rate(self, x)
+        x = _add_norm(self.layernorm, x, input, relu=True, link=link, drop=drop)
         return x if x.dtype == in_dtype else x.to(in_dtype)
 
 

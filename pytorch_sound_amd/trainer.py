@@ -195,6 +195,12 @@ class Trainer:
         torch.manual_seed(self.seed)
         if torch.cuda.is_available():
             torch.cuda.manual_seed(self.seed)
+            # the dropout masks of the HIP kernels (kernels.GroupNorm1, drop=): every rank draws its own, a resumed run does not repeat step 0's
+            # (a model that is not on a GPU leaves the device alone: a later first use starts from torch.initial_seed(), this seed, at call 0)
+            p0 = next(iter(self.model.parameters()), None)
+            if p0 is not None and p0.is_cuda:
+                from pytorch_sound_amd import kernels as K
+                K.dropout_seed(self.seed, call=(pdist.rank() << 48) + (self.step << 20), device=p0.device)
 
         if self.step == 0 and pretrained_path:
             self.load_pretrained_model()

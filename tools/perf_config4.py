@@ -3,7 +3,8 @@
 inside a bucket (BucketRandomBatchSampler), ragged pinned batch -> side-stream copy -> psnd_pad_collate (DevicePrefetcher, Tmax
 rounded to 4096 samples so that step shapes repeat), 80-mel log-mel features (psnd_logmel_fwd), 1x1 projection ->
 PositionalEncoding -> MultiHeadAttention(256, 4) -> PointwiseFeedForward with the padding mask, masked L1, Adam; steps replayed
-as hipGraphs per batch shape (Trainer.graph_steps, bounded cache).  Prints ms/step and audio-s/s (real, unpadded seconds)."""
+as hipGraphs per batch shape (Trainer.graph_steps, bounded cache).  Prints ms/step and audio-s/s (real, unpadded seconds).
+`--dropout P`: the two blocks' dropout rate (default 0.0: none; with 0 < P < 1 the norm kernels apply it, psnd_groupnorm1_drop_*)."""
 import os
 import sys
 import tempfile
@@ -20,6 +21,7 @@ from pytorch_sound_amd import optim as poptim  # noqa: E402
 
 dev = torch.device('cuda:0')
 SR, HOP, NB = 22050, 256, 32
+DROPOUT = float(sys.argv[sys.argv.index('--dropout') + 1]) if '--dropout' in sys.argv else 0.0
 MULT = int(os.environ.get('MULT', 22016))     # Tmax granularity (a multiple of the hop: 86 frames ~ 1 s): step shapes repeat -> few graphs
 
 
@@ -41,8 +43,8 @@ class Net(torch.nn.Module):
         super().__init__()
         self.inp = torch.nn.Conv1d(80, C, 1)
         self.pe = PositionalEncoding(C, 2048)
-        self.mha = MultiHeadAttention(C, H, 0.0)
-        self.ffn = PointwiseFeedForward(C, 0.0)
+        self.mha = MultiHeadAttention(C, H, DROPOUT)
+        self.ffn = PointwiseFeedForward(C, DROPOUT)
         self.out = torch.nn.Conv1d(C, 80, 1)
 
     def forward(self, mel, pad_mask):
@@ -109,8 +111,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     audio = float(torch.stack(secs).sum())
-    print('config 4 (%s): %.2f ms/step, %.1f k audio-s/s (unpadded); %d step graphs cached' % (
-        'hipGraph' if tr.graph_steps else 'eager', dt / steps * 1e3, audio / dt / 1e3,
+    print('config 4 (%s, dropout %g): %.2f ms/step, %.1f k audio-s/s (unpadded); %d step graphs cached' % (
+        'hipGraph' if tr.graph_steps else 'eager', DROPOUT, dt / steps * 1e3, audio / dt / 1e3,
         len([1 for v in getattr(tr, '_graphs', {}).values() if 'graph' in v])))
 
 
