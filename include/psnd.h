@@ -530,6 +530,38 @@ int psnd_stft_bwd_msl(const float *wav, int64_t N, int64_t T, int n_fft, int hop
                       float mag_eps, const float *t_mag, const float *norms, const float *g3, int L, float eps,
                       int accumulate, float *gwav, void *stream);
 
+/* ---- models/sound.py: InversePreEmphasis (:84-99) and VolNormConv (:7-60) ----------------------------------------------------------
+ *  psnd_ipreemph_fwd: y[n][t] = tanh(w_ih x[n][t] + w_hh y[n][t-1]), y[n][-1] = 0 - the one-unit bias-free tanh RNN.  x, y : (N, T) fp32.
+ *      w_ih, w_hh : DEVICE pointers to one float each (the RNN's own parameters: read at run time, so nothing the caller cached can go
+ *      stale).  `warm` selects the instance:
+ *        a multiple of 32 in [32, PSND_IPREEMPH_WARM_MAX]: the scan parallel over time - every lane owns 32 samples and first runs over the
+ *            `warm` samples before them from state 0 (from the clip start, where the state is exactly 0, if that is nearer), which leaves
+ *            an error <= 2 |w_hh|^warm in its first sample.  The caller's rule: the smallest such warm with 2 |w_hh|^warm <= 2^-25;
+ *        PSND_IPREEMPH_SEQ: one lane per clip, exact for any w_hh - for |w_hh| >= 1 and wherever the rule asks for more than WARM_MAX;
+ *        PSND_IPREEMPH_AUTO: the kernel applies that rule to *w_hh itself (no host copy of the weight needed, graph-capturable).
+ *  psnd_ipreemph_bwd: with d[t] = (1 - y[t]^2) (gy[t] + w_hh d[t+1]), d[T] = 0:  gx[t] = w_ih d[t] (fully overwritten),
+ *      gw[0] = sum d[t] x[t] (gradient of w_ih), gw[1] = sum d[t] y[t-1] (of w_hh), over all clips.  Same instances, mirrored in time.
+ *      partial : scratch of 2 * 256 * N * ceil(T / PSND_IPREEMPH_SPAN) doubles, every entry used is written first; a second launch adds
+ *      them in index order (no atomics: gw is bit-reproducible).
+ *  psnd_volnorm_fwd: hop i (start = i * hop, one for every start < L - window) - std[i] = unbiased standard deviation of all B * window
+ *      elements wav[:, start : start + window] (two passes in double), out[:, start : stop] = wav[:, start : stop] / (std[i] * inv_gain),
+ *      inv_gain = 1 / 10^(target_db / 10); stop = start + hop, for the last hop out_len - the caller applies the reference's tail rule
+ *      (models/sound.py volnorm_layout).  wav (B, L), out (B, out_len), std : one float per hop, all fully overwritten.
+ *  psnd_volnorm_reverse: the same tiling, out[:, start : stop] = wav[:, start : stop] * (std[i] / gain), gain = 10^(target_db / 10), std
+ *      read. */
+#define PSND_IPREEMPH_SPAN 8192
+#define PSND_IPREEMPH_WARM_MAX 2048
+#define PSND_IPREEMPH_SEQ (-1)
+#define PSND_IPREEMPH_AUTO (-2)
+int psnd_ipreemph_fwd(const float *x, int64_t N, int64_t T, const float *w_ih, const float *w_hh, int warm, float *y,
+                      void *stream);
+int psnd_ipreemph_bwd(const float *gy, const float *y, const float *x, int64_t N, int64_t T, const float *w_ih,
+                      const float *w_hh, int warm, float *gx, double *partial, float *gw, void *stream);
+int psnd_volnorm_fwd(const float *wav, int64_t B, int64_t L, int window, int hop, float inv_gain, float *out,
+                     int64_t out_len, float *std, void *stream);
+int psnd_volnorm_reverse(const float *wav, int64_t B, int64_t L, int window, int hop, float gain, const float *std,
+                         float *out, int64_t out_len, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

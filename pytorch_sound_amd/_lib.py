@@ -119,6 +119,10 @@ SIGNATURES = {
     'psnd_polar_bwd': (_INT, [_P, _P, _P, _P, _I64, _P, _P, _P]),
     'psnd_preemphasis_fwd': (_INT, [_P, _I64, _I64, _F, _P, _P]),
     'psnd_preemphasis_bwd': (_INT, [_P, _I64, _I64, _F, _P, _P]),
+    'psnd_ipreemph_fwd': (_INT, [_P, _I64, _I64, _P, _P, _INT, _P, _P]),
+    'psnd_ipreemph_bwd': (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _INT, _P, _P, _P, _P]),
+    'psnd_volnorm_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _F, _P, _I64, _P, _P]),
+    'psnd_volnorm_reverse': (_INT, [_P, _I64, _I64, _INT, _INT, _F, _P, _P, _I64, _P]),
     'psnd_stft_loss_blocks': (_I64, [_I64]),
     'psnd_stft_loss_partial': (_INT, [_P, _P, _I64, _I64, _F, _P, _P]),
     'psnd_stft_loss_final': (_INT, [_P, _P, _INT, _I64, _P, _P, _P]),

@@ -935,6 +935,77 @@ class PreEmphasisFn(torch.autograd.Function):
         return gx, None
 
 
+IPREEMPH_SPAN, IPREEMPH_WARM_MAX, IPREEMPH_SEQ, IPREEMPH_AUTO = 8192, 2048, -1, -2        # include/psnd.h
+
+
+class InversePreEmphasisFn(torch.autograd.Function):
+    """y[t] = tanh(w_ih x[t] + w_hh y[t-1]), y[-1] = 0, on (N, 1, T) fp32 - the one-unit tanh RNN of sound.py:84-99 (psnd_ipreemph_*).
+    `w_ih`, `w_hh`: the RNN's (1, 1) parameters on the input's device; the kernels read them there, so no host copy can be stale.
+    `warm`: IPREEMPH_AUTO (the kernel applies the warm-up rule to w_hh), IPREEMPH_SEQ, or a warm-up length (psnd.h)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, warm=IPREEMPH_AUTO):
+        _need_cuda(x, 'input')
+        for w, name in ((w_ih, 'weight_ih'), (w_hh, 'weight_hh')):
+            _need_cuda(w, name)
+            if w.numel() != 1 or w.device != x.device:
+                raise _lib.PsndError('InversePreEmphasis: %s must hold one element on %s, got %s on %s'
+                                     % (name, x.device, tuple(w.shape), w.device))
+        x = x.contiguous()
+        T = x.shape[-1]
+        N = x.numel() // max(T, 1)
+        y = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            check(lib().psnd_ipreemph_fwd(ptr(x), N, T, ptr(w_ih), ptr(w_hh), int(warm), ptr(y), stream_ptr(x.device)), 'psnd_ipreemph_fwd')
+        ctx.save_for_backward(x, y, w_ih, w_hh)
+        ctx.warm = int(warm)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, w_ih, w_hh = ctx.saved_tensors
+        gy = gy.contiguous()
+        T = x.shape[-1]
+        N = x.numel() // max(T, 1)
+        gx = torch.empty_like(x)
+        partial = torch.empty(2 * 256 * max(N, 1) * max((T + IPREEMPH_SPAN - 1) // IPREEMPH_SPAN, 1), dtype=torch.float64, device=x.device)
+        gw = torch.empty(2, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            check(lib().psnd_ipreemph_bwd(ptr(gy), ptr(y), ptr(x), N, T, ptr(w_ih), ptr(w_hh), ctx.warm, ptr(gx), ptr(partial), ptr(gw),
+                                          stream_ptr(x.device)), 'psnd_ipreemph_bwd')
+        need = ctx.needs_input_grad
+        return (gx if need[0] else None, gw[0].reshape(w_ih.shape) if need[1] else None, gw[1].reshape(w_hh.shape) if need[2] else None, None)
+
+
+def volnorm_forward(wav, window, hop, inv_gain, out_len):
+    """psnd_volnorm_fwd: wav (B, L) fp32 -> (out (B, out_len), std (hops,)), one workgroup per hop; out_len from sound.volnorm_layout"""
+    _need_cuda(wav, 'wav')
+    wav = wav.contiguous()
+    B, L = wav.shape
+    hops = (L - window + hop - 1) // hop
+    out = torch.empty((B, out_len), dtype=torch.float32, device=wav.device)
+    std = torch.empty(hops, dtype=torch.float32, device=wav.device)
+    with torch.cuda.device(wav.device):
+        check(lib().psnd_volnorm_fwd(ptr(wav), B, L, int(window), int(hop), float(inv_gain), ptr(out), int(out_len), ptr(std),
+                                     stream_ptr(wav.device)), 'psnd_volnorm_fwd')
+    return out, std
+
+
+def volnorm_reverse(wav, window, hop, gain, std, out_len):
+    """psnd_volnorm_reverse: wav (B, L) fp32 and the hops' deviations std (>= hops,) on the device -> out (B, out_len)"""
+    _need_cuda(wav, 'wav')
+    _need_cuda(std, 'std')
+    wav, std = wav.contiguous(), std.contiguous()
+    B, L = wav.shape
+    if std.numel() < (L - window + hop - 1) // hop:
+        raise _lib.PsndError('volnorm_reverse: %d deviations for %d hops' % (std.numel(), (L - window + hop - 1) // hop))
+    out = torch.empty((B, out_len), dtype=torch.float32, device=wav.device)
+    with torch.cuda.device(wav.device):
+        check(lib().psnd_volnorm_reverse(ptr(wav), B, L, int(window), int(hop), float(gain), ptr(std), ptr(out), int(out_len),
+                                         stream_ptr(wav.device)), 'psnd_volnorm_reverse')
+    return out
+
+
 def _msl_fused(n_fft, hop):
     """psnd_stft_bwd_msl takes this resolution (PSND_MSL_FUSED=0: the two-launch path, for A/B runs and tests)."""
     import os

@@ -1,9 +1,10 @@
 """Drop-in for pytorch_sound/models/sound.py: VolNormConv, PreEmphasis, InversePreEmphasis, build_stft_functions,
 multi_stft_loss - same names, arguments and results.
 
-On a HIP device PreEmphasis and multi_stft_loss run on libpsnd_hip.so (psnd_preemphasis_*, psnd_stft_fwd/bwd,
+On a HIP device every class here runs on libpsnd_hip.so (psnd_volnorm_*, psnd_preemphasis_*, psnd_ipreemph_*, psnd_stft_fwd/bwd,
 psnd_stft_loss_*); CPU tensors take the reference's torch formulation (host-side use: tests, data preparation).
 """
+import math
 from typing import List, Tuple
 
 import torch
@@ -13,10 +14,27 @@ from pytorch_sound_amd import kernels as K
 from pytorch_sound_amd.models.transforms import STFTTorchAudio as STFT
 
 
+def volnorm_layout(L: int, window: int, hop: int, reverse: bool = False) -> Tuple[int, int, int]:
+    """What the slicing loops of VolNormConv do to a signal of L samples, as numbers: (n_hops, out_len, tail_start).
+    Hop i starts at i * hop, one for every start < L - window.  It covers [start, start + hop), except that a hop with
+    start >= tail_start runs to the end of the signal (forward: L - window - 1, reverse: L - window - hop; only the last hop can).
+    The slices tile [0, out_len) without gaps.  No hop (L <= window): (0, 0, tail_start)."""
+    last = L - window
+    tail_start = last - (hop if reverse else 1)
+    if last <= 0:
+        return 0, 0, tail_start
+    n_hops = (last + hop - 1) // hop
+    start = (n_hops - 1) * hop
+    return n_hops, (L if start >= tail_start else min(start + hop, L)), tail_start
+
+
 class VolNormConv:
     """Windowed volume normalisation (sound.py:7-60): every hop-sized slice is divided by the standard deviation of
     the window starting there, scaled to ``target_db``; ``reverse`` undoes it with the remembered deviations.
-    Host-side utility (python loop over hops on ``.data``, exactly the reference's slicing rules)."""
+    CPU tensors: python loop over hops on ``.data``, exactly the reference's slicing rules.  HIP tensors: one launch of
+    psnd_volnorm_fwd / psnd_volnorm_reverse (one workgroup per hop) and one copy of the deviations - device to host into
+    ``std_buffer`` after ``forward`` (which therefore cannot be captured into a graph), host to device before ``reverse``,
+    which reads ``std_buffer`` as the reference does.  The result is detached either way."""
 
     def __init__(self, window_size: int, hop_size: int, target_db: float):
         self.window_size = window_size
@@ -32,9 +50,19 @@ class VolNormConv:
     def _scale(self, std):
         return std / 10 ** (self.target_db / 10)
 
+    def _native(self, wav: torch.Tensor) -> bool:
+        """a HIP tensor takes the kernels; no hop (today's error) and non-floating input (today's error) take the loop below"""
+        return wav.is_cuda and wav.is_floating_point() and wav.size(-1) > self.window_size and wav.numel() > 0
+
     def forward(self, wav: torch.Tensor) -> torch.Tensor:
         wav_len = wav.size(-1)
         self.init_buffer(wav_len)
+        if self._native(wav):
+            n_hops, out_len, _ = volnorm_layout(wav_len, self.window_size, self.hop_size)
+            out, std = K.volnorm_forward(wav.data.reshape(-1, wav_len).float(), self.window_size, self.hop_size,
+                                         1.0 / 10 ** (self.target_db / 10), out_len)
+            self.std_buffer[:n_hops] = std.cpu()                                # an entry the loop never writes stays 0
+            return out.to(wav.dtype).reshape(wav.shape[:-1] + (out_len,))
         last = wav_len - self.window_size
         chunks = []
         for idx, start in enumerate(range(0, last, self.hop_size)):
@@ -47,6 +75,13 @@ class VolNormConv:
     def reverse(self, wav: torch.Tensor) -> torch.Tensor:
         wav_len = wav.size(-1)
         assert self.prev_wav_len >= wav_len, '{} is smaller than {} !'.format(self.prev_wav_len, wav_len)
+        if self._native(wav):
+            n_hops, out_len, _ = volnorm_layout(wav_len, self.window_size, self.hop_size, reverse=True)
+            self.std_buffer[n_hops - 1]                                         # a buffer cut short by the user: the loop's IndexError
+            std = self.std_buffer[:n_hops].to(device=wav.device, dtype=torch.float32)
+            out = K.volnorm_reverse(wav.data.reshape(-1, wav_len).float(), self.window_size, self.hop_size, 10 ** (self.target_db / 10),
+                                    std, out_len)
+            return out.to(wav.dtype).reshape(wav.shape[:-1] + (out_len,))
         last = wav_len - self.window_size
         chunks = []
         for idx, start in enumerate(range(0, last, self.hop_size)):
@@ -75,9 +110,29 @@ class PreEmphasis(torch.nn.Module):
         return F.conv1d(input, self.flipped_filter)
 
 
+def ipreemph_warm(w_hh: float) -> int:
+    """Warm-up length of the time-parallel scan of InversePreEmphasis for a recurrent weight, or K.IPREEMPH_SEQ.
+    h -> tanh(a + w_hh h) contracts by |w_hh| and |h| <= 1, so a lane that starts W samples early from h = 0 is within 2 |w_hh|^W of
+    the true state when it reaches its chunk.  W is the smallest multiple of 32 (at least 32) with 2 |w_hh|^W <= 2^-25; if that exceeds
+    K.IPREEMPH_WARM_MAX (|w_hh| > 0.9912), and for |w_hh| >= 1 or NaN, where nothing contracts, the sequential instance runs.  The kernels
+    apply the same rule to the weight they read on the device (psnd.h, PSND_IPREEMPH_AUTO)."""
+    a = abs(float(w_hh))
+    if not a < 1.0:
+        return K.IPREEMPH_SEQ
+    if a < 2.0 ** -26:
+        return 32
+    w = math.ceil(26.0 * math.log(2.0) / -math.log(a))
+    if not w <= K.IPREEMPH_WARM_MAX:
+        return K.IPREEMPH_SEQ
+    return max(32, (w + 31) // 32 * 32)
+
+
 class InversePreEmphasis(torch.nn.Module):
     """sound.py:84-99 verbatim in behaviour: a 1-unit ``torch.nn.RNN`` (default tanh non-linearity, as in the
-    reference) with input weight 1 and recurrent weight ``coef`` - a sequential scan, inference-side only."""
+    reference) with input weight 1 and recurrent weight ``coef``: h[t] = tanh(w_ih x[t] + w_hh h[t-1]).
+    A HIP tensor takes psnd_ipreemph_* - a scan parallel over time (``ipreemph_warm``), differentiable in the input and both weights.
+    The kernels read ``rnn.weight_ih_l0`` / ``weight_hh_l0`` on the device at run time, never ``coef``: a loaded checkpoint or an
+    in-place edit (``.data.fill_`` included, which no version counter sees) counts on the next call, and the call can be captured."""
 
     def __init__(self, coef: float = 0.97):
         super().__init__()
@@ -87,6 +142,15 @@ class InversePreEmphasis(torch.nn.Module):
         self.rnn.weight_hh_l0.data.fill_(self.coef)
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if input.is_cuda:                                   # a HIP tensor always takes psnd_ipreemph_* (fp32 kernel: cast in and out)
+            if input.dim() != 3 or input.size(1) != 1 or not input.is_floating_point():
+                raise RuntimeError('InversePreEmphasis expects a floating-point (N, 1, T) tensor, got %s %s' % (input.dtype, tuple(input.shape)))
+            w_ih, w_hh = self.rnn.weight_ih_l0, self.rnn.weight_hh_l0
+            if w_ih.device != input.device or w_hh.device != input.device:
+                raise RuntimeError('Input and parameter tensors are not at the same device, found input tensor at %s and parameter tensor at %s'
+                                   % (input.device, w_hh.device))
+            y = K.InversePreEmphasisFn.apply(input.float(), w_ih.float(), w_hh.float())
+            return y if y.dtype == input.dtype else y.to(input.dtype)
         x, _ = self.rnn(input.transpose(1, 2))
         return x.transpose(1, 2)
 
