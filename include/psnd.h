@@ -120,6 +120,44 @@ int psnd_polar_bwd(const float *gmag, const float *gphase, const float *mag, con
 int psnd_istft(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop,
                const void *plan, float eps, float *out, void *stream);
 
+/* ---- mixed-radix STFT: the three transforms above for the n_fft the power-of-two kernels leave out -----------------------------
+ *  Covered: even n_fft = 2^a 3^b 5^c in [16, 4096] that is no power of two (400, 480, 600, 800, 960, 1200, 2400, 4000 ...: what
+ *  STFTTorchAudio / Audio2Mel / LogMelSpectrogramTorchAudio / interface MelSpectrogram / multi_stft_loss meet at speech sample rates,
+ *  transforms.py:271-366, sound.py:89-133).  Powers of two stay with psnd_stft_* (psnd_stft_plan_bytes(1000) is still 0).
+ *
+ *  Plan (psnd_stft_mr_plan_bytes(n_fft) = 4 (16 + 3 n_fft) bytes, 0 for an uncovered size), in 4-byte words:
+ *    [0, 16)            int32 header: magic 0x3152464d, n_fft, P = number of passes, radix[0 .. P) in execution order - every factor 5,
+ *                       then every 3, then every 4, then one 2 if a factor two is left (the product is n_fft) - zeros behind
+ *    [16, 16 + n)       the window, n_fft fp32 taps as given (already centre-padded)
+ *    [16 + n, 16 + 3n)  (cos, -sin)(2 pi j / n_fft), j < n_fft, computed in float64, one fp32 pair each
+ *  The compute entry points take the device copy and its size: plan_bytes must equal psnd_stft_mr_plan_bytes(n_fft) (PSND_E_ARG - this
+ *  is how a plan of the other kind or of another size is told apart without reading device memory).
+ *
+ *  psnd_stft_mr_fwd: psnd_stft_fwd's contract - three framings, mag_eps inside the square root, any subset of mag / phase / (re, im),
+ *      each (N, K, F) fp32 fully overwritten; the reflect padding is index arithmetic, rows of wav need 4-byte alignment only.
+ *  psnd_stft_mr_bwd: psnd_stft_bwd's contract (gmag and / or (gre, gim) -> gwav (N, T), fully overwritten; a bin with mag == 0 and
+ *      mag_eps == 0 gives NaN as there).  Two launches and no float atomic: window * adjoint DFT of every frame goes to `scratch`
+ *      (psnd_stft_mr_bwd_scratch_bytes(N, T, n_fft, hop, framing) bytes = 4 N F n_fft, device memory the caller provides), then every
+ *      sample of gwav adds up the frame taps that read it - the sample itself, its left and its right mirror image under the reflect
+ *      padding, frames ascending - so the result is bit-reproducible.
+ *  psnd_istft_mr: psnd_istft's definition (windowed inverse real DFT of mag e^{i phase}, the imaginary parts of DC and Nyquist dropped,
+ *      overlap-add, divided by the squared-window envelope + eps, n_fft / 2 trimmed on both sides; out (N, (F - 1) hop) fully overwritten;
+ *      eps = 0 is torch.istft's convention) with the same two launches; psnd_istft_mr_scratch_bytes(N, F, n_fft) = 4 N F n_fft.
+ *
+ *  PSND_E_ARG without touching the device: a NULL required pointer, hop <= 0, a bad framing, plan_bytes of another plan, a scratch that is
+ *  NULL or too small; PSND_E_SHAPE: T <= the reflect pad, index ranges beyond 2^31, N > 65535; PSND_E_UNSUPPORTED: an uncovered n_fft. */
+size_t psnd_stft_mr_plan_bytes(int n_fft);
+int psnd_stft_mr_plan_build(int n_fft, const float *window_host, void *plan_host);
+int psnd_stft_mr_fwd(const float *wav, int64_t N, int64_t T, int n_fft, int hop, int framing, const void *plan, size_t plan_bytes,
+                     float mag_eps, float *mag, float *phase, float *re, float *im, void *stream);
+size_t psnd_stft_mr_bwd_scratch_bytes(int64_t N, int64_t T, int n_fft, int hop, int framing);
+int psnd_stft_mr_bwd(const float *wav, int64_t N, int64_t T, int n_fft, int hop, int framing, const void *plan, size_t plan_bytes,
+                     float mag_eps, const float *gmag, const float *gre, const float *gim, void *scratch, size_t scratch_bytes,
+                     float *gwav, void *stream);
+size_t psnd_istft_mr_scratch_bytes(int64_t N, int64_t F, int n_fft);
+int psnd_istft_mr(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop, const void *plan, size_t plan_bytes,
+                  float eps, void *scratch, size_t scratch_bytes, float *out, void *stream);
+
 /* ---- mel projection + log + clamp: replaces transforms.py:235-243, :364-365,
  *      interface/hifi_gan.py:58-61 -------------------------------------------------------- */
 #define PSND_LOG_NONE 0  /* linear mel                                   */

@@ -39,6 +39,13 @@ SIGNATURES = {
     'psnd_stft_mag_nfk': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P]),
     'psnd_stft_bwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P, _P, _P, _P]),
     'psnd_istft': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _F, _P, _P]),
+    'psnd_stft_mr_plan_bytes': (_c.c_size_t, [_INT]),
+    'psnd_stft_mr_plan_build': (_INT, [_INT, _P, _P]),
+    'psnd_stft_mr_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _c.c_size_t, _F, _P, _P, _P, _P, _P]),
+    'psnd_stft_mr_bwd_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT, _INT, _INT]),
+    'psnd_stft_mr_bwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _c.c_size_t, _F, _P, _P, _P, _P, _c.c_size_t, _P, _P]),
+    'psnd_istft_mr_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT]),
+    'psnd_istft_mr': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P]),
     'psnd_mel_plan_bytes': (_c.c_size_t, [_INT, _INT]),
     'psnd_mel_plan_build': (_INT, [_INT, _INT, _P, _P]),
     'psnd_mel_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P]),
@@ -283,6 +290,27 @@ def build_stft_plan(n_fft, window):
         raise PsndError('stft plan: n_fft=%d unsupported (power of two in [16, 8192])' % n_fft)
     plan = np.zeros(nb, dtype=np.uint8)
     check(lib().psnd_stft_plan_build(int(n_fft), np_ptr(w), np_ptr(plan)), 'psnd_stft_plan_build')
+    return plan
+
+
+STFT_MR_SIZES = 'even 2^a 3^b 5^c in [16, 4096]: 400, 480, 600, 800, 960, 1200, 2400, 4000 ...'
+
+
+def stft_mr_covered(n_fft):
+    """True where the mixed-radix STFT kernels (psnd_stft_mr_*) take this n_fft; powers of two belong to psnd_stft_*"""
+    return lib().psnd_stft_mr_plan_bytes(int(n_fft)) > 0
+
+
+def build_stft_mr_plan(n_fft, window):
+    """plan of the mixed-radix kernels (header, window, twiddle table: include/psnd.h).  window: n_fft taps, already centre-padded."""
+    w = np.ascontiguousarray(np.asarray(window, dtype=np.float32))
+    if w.shape != (n_fft,):
+        raise PsndError('stft plan: window must have n_fft=%d taps, got %s' % (n_fft, w.shape))
+    nb = lib().psnd_stft_mr_plan_bytes(int(n_fft))
+    if nb == 0:
+        raise PsndError('stft plan: n_fft=%d unsupported by the mixed-radix kernels (%s)' % (n_fft, STFT_MR_SIZES))
+    plan = np.zeros(nb, dtype=np.uint8)
+    check(lib().psnd_stft_mr_plan_build(int(n_fft), np_ptr(w), np_ptr(plan)), 'psnd_stft_mr_plan_build')
     return plan
 
 

@@ -35,8 +35,42 @@ def plan_tensor(plan_np):
     return torch.from_numpy(np.ascontiguousarray(plan_np))
 
 
+PLAN_POW2, PLAN_MR = 'pow2', 'mixed-radix'
+_MR_BYTES = {}
+
+
+def _mr_plan_bytes(n_fft):
+    nb = _MR_BYTES.get(n_fft)
+    if nb is None:
+        nb = _MR_BYTES[n_fft] = int(lib().psnd_stft_mr_plan_bytes(int(n_fft)))
+    return nb
+
+
 def stft_plan(n_fft, window):
-    return plan_tensor(_lib.build_stft_plan(n_fft, window))
+    """plan of the STFT kernels for this n_fft: a power of two gets the plan of psnd_stft_* as ever, an even 2^a 3^b 5^c up to 4096 the
+    plan of the mixed-radix kernels (psnd_stft_mr_*).  The tensor carries `psnd_plan_kind`; that attribute does not survive `.to(device)`,
+    so the launchers tell the kinds apart by stft_plan_kind: the two plans of one n_fft never coexist and their sizes are fixed by n_fft."""
+    n_fft = int(n_fft)
+    if _mr_plan_bytes(n_fft) > 0:
+        plan = plan_tensor(_lib.build_stft_mr_plan(n_fft, window))
+        plan.psnd_plan_kind = PLAN_MR
+        return plan
+    if int(lib().psnd_stft_plan_bytes(n_fft)) == 0:
+        raise _lib.PsndError('stft plan: n_fft=%d unsupported: the STFT kernels cover powers of two in [16, 8192] and %s'
+                             % (n_fft, _lib.STFT_MR_SIZES))
+    plan = plan_tensor(_lib.build_stft_plan(n_fft, window))
+    plan.psnd_plan_kind = PLAN_POW2
+    return plan
+
+
+def stft_plan_kind(plan, n_fft):
+    """PLAN_MR / PLAN_POW2 of a plan built by stft_plan(n_fft, ...), on any device"""
+    nb = _mr_plan_bytes(int(n_fft))
+    return PLAN_MR if nb > 0 and plan.numel() * plan.element_size() == nb else PLAN_POW2
+
+
+def _plan_bytes(plan):
+    return int(plan.numel() * plan.element_size())
 
 
 def mel_plan(mel_filter):
@@ -73,8 +107,12 @@ def stft_forward(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0,
         if ev is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        check(lib().psnd_stft_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps),
-                                  ptr(mag), ptr(phase), ptr(re), ptr(im), stream_ptr(wav.device)), 'psnd_stft_fwd')
+        if stft_plan_kind(plan, n_fft) == PLAN_MR:
+            check(lib().psnd_stft_mr_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), _plan_bytes(plan), float(mag_eps),
+                                         ptr(mag), ptr(phase), ptr(re), ptr(im), stream_ptr(wav.device)), 'psnd_stft_mr_fwd')
+        else:
+            check(lib().psnd_stft_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps),
+                                      ptr(mag), ptr(phase), ptr(re), ptr(im), stream_ptr(wav.device)), 'psnd_stft_fwd')
         if ev is not None:
             e1.record()
             ev.append((e0, e1, N))
@@ -120,6 +158,14 @@ def stft_backward(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0, gm
             _need_cuda(g, 'grad')
     gwav = torch.empty_like(wav)
     with torch.cuda.device(wav.device):
+        if stft_plan_kind(plan, n_fft) == PLAN_MR:
+            # two launches: the windowed frame gradients go through a scratch, every sample gathers its frames in a fixed order
+            nb = int(lib().psnd_stft_mr_bwd_scratch_bytes(N, T, n_fft, hop, framing))
+            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=wav.device)
+            check(lib().psnd_stft_mr_bwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), _plan_bytes(plan), float(mag_eps),
+                                         ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(scratch), scratch.numel() * 4, ptr(gwav),
+                                         stream_ptr(wav.device)), 'psnd_stft_mr_bwd')
+            return gwav
         check(lib().psnd_stft_bwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps),
                                   ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gwav), stream_ptr(wav.device)),
               'psnd_stft_bwd')
@@ -349,6 +395,12 @@ def istft_forward(magnitude, phase, n_fft, hop, plan, eps=1e-9):
                              % (n_fft // 2 + 1, tuple(magnitude.shape), tuple(phase.shape)))
     out = torch.empty((N, max((F - 1) * hop, 0)), dtype=torch.float32, device=magnitude.device)
     with torch.cuda.device(magnitude.device):
+        if stft_plan_kind(plan, n_fft) == PLAN_MR:
+            nb = int(lib().psnd_istft_mr_scratch_bytes(N, F, n_fft))
+            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=magnitude.device)
+            check(lib().psnd_istft_mr(ptr(magnitude), ptr(phase), N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
+                                      ptr(scratch), scratch.numel() * 4, ptr(out), stream_ptr(magnitude.device)), 'psnd_istft_mr')
+            return out
         check(lib().psnd_istft(ptr(magnitude), ptr(phase), N, F, n_fft, hop, ptr(plan), float(eps), ptr(out),
                                stream_ptr(magnitude.device)), 'psnd_istft')
     return out
@@ -1009,7 +1061,27 @@ def volnorm_reverse(wav, window, hop, gain, std, out_len):
 def _msl_fused(n_fft, hop):
     """psnd_stft_bwd_msl takes this resolution (PSND_MSL_FUSED=0: the two-launch path, for A/B runs and tests)."""
     import os
-    return _sw.lab('PSND_MSL_FUSED', '1') != '0' and bool(lib().psnd_stft_bwd_msl_supported(int(n_fft), int(hop)))
+    return (_sw.lab('PSND_MSL_FUSED', '1') != '0' and _mr_plan_bytes(int(n_fft)) == 0
+            and bool(lib().psnd_stft_bwd_msl_supported(int(n_fft), int(hop))))
+
+
+MSL_SIZES = 'powers of two in [16, 8192] and the multiples of 16 among the even 2^a 3^b 5^c up to 4096: 400, 480, 640, 800, 960, 1200, 1600, 2400 ...'
+
+
+def msl_covered(n_fft):
+    """multi_stft_loss takes this n_fft on a HIP tensor.  Narrower than stft_plan on purpose: the loss has always refused n_fft = 1000
+    (8 * 125) and that refusal is part of its tested contract, so of the mixed-radix sizes it admits the multiples of 16 - every framing
+    in use at 16 / 24 / 48 kHz but 600 and 1000."""
+    n_fft = int(n_fft)
+    if _mr_plan_bytes(n_fft) > 0:
+        return n_fft % 16 == 0
+    return int(lib().psnd_stft_plan_bytes(n_fft)) > 0
+
+
+def msl_check(n_ffts):
+    for n_fft in n_ffts:
+        if not msl_covered(n_fft):
+            raise _lib.PsndError('multi_stft_loss: n_fft=%d unsupported on a HIP tensor (%s)' % (n_fft, MSL_SIZES))
 
 
 class MultiStftLossFn(torch.autograd.Function):
@@ -1026,6 +1098,7 @@ class MultiStftLossFn(torch.autograd.Function):
         if pred.shape != target.shape or pred.dim() != 2:
             raise _lib.PsndError('multi_stft_loss: pred %s and target %s must be equal (N, T) shapes'
                                  % (tuple(pred.shape), tuple(target.shape)))
+        msl_check(n for n, _ in cfgs)
         pred, target = pred.contiguous(), target.contiguous()
         N = pred.shape[0]
         L = len(cfgs)

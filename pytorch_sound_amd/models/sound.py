@@ -186,6 +186,7 @@ def multi_stft_loss(pred: torch.Tensor, target: torch.Tensor, stft_params: List[
     """
     funcs = build_stft_functions(*stft_params)
     if pred.is_cuda:
+        K.msl_check(f.n_fft for f in funcs)          # before any plan is built
         cfgs = tuple((f.n_fft, f.hop_length) for f in funcs)
         plans = [f._plan(pred.device) for f in funcs]
         out = K.MultiStftLossFn.apply(pred.float(), target.float(), eps, cfgs, *plans)
