@@ -14,9 +14,19 @@
 //     first conv reads; the residual stream (rounded to bf16 exactly as the tensor a pair launch writes) stays in registers in the
 //     accumulator layout.  No transposing fp32 epilogue through LDS, no global round trip between pairs; the tensors the backward needs
 //     (mid, raw, activated of every pair) are copied out of LDS with 16-byte stores while the next conv runs.
+//   * CHANNEL-CONTIGUOUS accumulators: the MFMA takes the weight fragment as its first operand and the tile fragment as its second
+//     (v_mfma_f32_32x32x16_bf16 has one lane map for both), so a lane holds ONE tile row and, in registers 4 g ... 4 g + 3, four consecutive
+//     channels = one aligned 8-byte word of the row-major tile the next conv reads.  An epilogue is 8 `ds_write_b64` per tile written and
+//     row block instead of 32 `ds_write_b16`, one row mask per row block instead of one per value pair, float4 bias reads from a 4 KB LDS
+//     table and (masked form) one 32-bit word of mask bits per row block instead of a byte per value.  The sums are the same products in
+//     the same order (tools/mb/probe_mfma_swap.hip: 0 differing words), the results bit-identical to the row-contiguous layout the pair
+//     kernels keep.  Measured (tools/trace_chain.py, 32 x 173 frames, a ResBlock1): a workgroup lives 62.2 k cycles instead of 65.1 k
+//     (forward) and 69.4 k instead of 78.5 k (masked); in the bench step 33.3 / 35.2 us per launch instead of 36.1 / 39.4 us; 150 / 170
+//     VGPRs instead of 230 / 254.  The 8-byte stores are 2-way bank conflicts (16 lanes of a store group share kg, rows 132 dwords apart:
+//     only 16 of 32 banks in reach): SQ_LDS_BANK_CONFLICT 0 -> 2.7 k cycles per workgroup, all LDS-array cycles +3 % forward, -6 % masked.
 //   * 64-row tiles: every B fragment (1 KB per wave and unit, straight from L2 in the fragment-ordered packs) feeds two MFMAs, so the
 //     weight stream (2.3 MB per workgroup and ResBlock through the CU's vector-memory path) and the matrix pipe are balanced.
-// LDS: act tile [80][264] + mid tile [80][264] + raw tile [64][264] bf16 = 118 KB: one 512-thread workgroup per CU.
+// LDS: act tile [80][264] + mid tile [80][264] + raw tile [64][264] bf16 = 118 KB + the 4 KB bias table: one 512-thread workgroup per CU.
 #include "psnd_conv_pair.h"
 
 #include <atomic>
@@ -63,6 +73,10 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
     static_assert(UNITS % RU == 0 && RU % 3 == 0, "the B ring turns whole");
     extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
     __shared__ unsigned char s_in[MROWS];
+    // bias rows of the two convs of a pair, [pair parity][conv][channel]: the epilogues read four consecutive channels as one float4.  Pair
+    // pp + 1's rows are requested at the top of pair pp and stored in its first epilogue (two workgroup barriers in front of their first
+    // reader, one behind the last reader of the rows they replace).  The masked form has no bias and no table.
+    __shared__ __attribute__((aligned(16))) float s_bias[BWD ? 1 : 2][BWD ? 4 : 2 * C];
     // Hand-over between the convs of the chain WITHOUT a workgroup barrier (-DPSND_CHAIN_FLAGS=1; measured, OFF by default): s_flag[g] counts the epilogues
     // the waves of group g (0: waves 0-3 = channels 0-127 of a tile, 1: waves 4-7 = channels 128-255) have finished.  A conv's loop may
     // start on k-steps 0-7 as soon as group 0 has written the tile's first half and needs group 1 only before k-step 8.  Why: a SIMD
@@ -97,7 +111,10 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
     };
     bf16_t *sXa = smem, *sM = smem + BR * RS, *sXr = smem + 2 * BR * RS;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, kg = lane >> 5;
-    const int col0 = wave * 32 + li;
+    // Accumulator layout (the weights are the MFMA's FIRST operand, see run_conv): acc[m][q] is tile row 32 m + li, channel
+    // 32 wave + (q & 3) + 8 (q >> 2) + 4 kg - registers 4 g ... 4 g + 3 are four consecutive channels cb + 8 g + {0 .. 3} of ONE row, one aligned
+    // 8-byte word of a row-major tile.  eo: this lane's element offset in a tile whose row 0 is at offset 0.
+    const int cb = wave * 32 + 4 * kg, eo = li * RS + cb;
     const long long g0 = (long long)blockIdx.x * p.ts - p.lo;
     const unsigned t_bytes = (unsigned)((size_t)p.R * C * sizeof(bf16_t)), w_bytes = (unsigned)(3u * C * C * sizeof(bf16_t));
     const __amdgpu_buffer_rsrc_t rA = make_uniform_rsrc(p.A, (int)t_bytes), rR = make_uniform_rsrc(p.res, (int)t_bytes);
@@ -166,6 +183,11 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
         const __amdgpu_buffer_rsrc_t rW = make_uniform_rsrc(p.d[0].W1, (int)w_bytes);
         static_for<0, RU>([&](auto uc) __attribute__((always_inline)) { fetch_b(uc, rW, 0); });
     }
+    ChainPair d = p.d[0];
+    if constexpr (!BWD) {
+        const float *bp = tid < C ? d.bias1 : d.bias2;
+        s_bias[0][tid] = bp ? bp[tid & (C - 1)] : 0.f;
+    }
     if (tid < MROWS) {
         const long long r = g0 + tid;
         const int l = (int)(((r % p.Lp) + p.Lp) % p.Lp);
@@ -197,9 +219,11 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int i = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * kg;
-            xres[m][q] = bf2f(BWD ? sXa[(HMAXP + i) * RS + col0] : sXr[i * RS + col0]);     // BWD: the residual IS the input gradient
+        for (int g = 0; g < 4; ++g) {
+            const bf16_t *src = BWD ? sXa + HMAXP * RS : sXr;                             // BWD: the residual IS the input gradient
+            const uint2 w = *reinterpret_cast<const uint2 *>(src + eo + m * 32 * RS + 8 * g);
+            xres[m][4 * g] = __builtin_bit_cast(float, w.x << 16), xres[m][4 * g + 1] = __builtin_bit_cast(float, w.x & 0xffff0000u);
+            xres[m][4 * g + 2] = __builtin_bit_cast(float, w.y << 16), xres[m][4 * g + 3] = __builtin_bit_cast(float, w.y & 0xffff0000u);
         }
 
     f32x16 acc[MB];
@@ -209,7 +233,10 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][i] = 0.f;
     };
-    // one conv over the haloed tile `src` (tile row i <-> buffer row i + HMAXP); the unit order is that of conv_pair_body::run_conv
+    // one conv over the haloed tile `src` (tile row i <-> buffer row i + HMAXP); the unit order is that of conv_pair_body::run_conv.
+    // The MFMA takes the weight fragment as its first operand and the tile fragment as its second (both have the same lane map: lane l
+    // holds row / column l & 31, k = 8 (l >> 5) + j), so the accumulator is the TRANSPOSE of conv_pair_body's: a lane holds one tile row
+    // and 16 channels.  Every element is the same 16 products per unit summed the same way (tools/mb/probe_mfma_swap.hip: bit-equal).
     // rWn: the pack of the NEXT conv - the last ring turn refills with its first units instead of out-of-range zeros, so the next loop
     // starts with a full ring and no wave spends ~700 cycles issuing twelve 1 KB loads between two loops
     auto run_conv = [&](const bf16_t *src, int off0, int dstep, __amdgpu_buffer_rsrc_t rW, __amdgpu_buffer_rsrc_t rWn, unsigned need) __attribute__((always_inline)) {
@@ -236,7 +263,7 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
                     afrag(std::integral_constant<int, u + AR - 1>{}, it, xr[(u + AR - 1) % AR]);
                     const bf16x8 b = __builtin_bit_cast(bf16x8, rb[u]);
 #pragma unroll
-                    for (int m = 0; m < MB; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xr[u % AR][m], b, acc[m], 0, 0, 0);
+                    for (int m = 0; m < MB; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, xr[u % AR][m], acc[m], 0, 0, 0);
                     fetch_b(uc, it + 1 < UNITS / RU ? rW : rWn, it + 1 < UNITS / RU ? it + 1 : 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, MB, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, MB, 0);
@@ -270,37 +297,45 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
         }
     };
 
-    // rows of this lane's accumulator elements that lie inside a clip, as AND masks on the packed bf16 pair of rows (i, i + 1):
-    // mw[m][q / 2] for accumulator elements q, q + 1 of row block m
-    unsigned mw[MB][8];
+    // this lane's rows that lie inside a clip, as AND masks on the packed bf16 words of row 32 m + li
+    unsigned rmask[MB];
 #pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const int i = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * kg;
-            mw[m][q / 2] = (s_in[i] ? 0xffffu : 0u) | (s_in[i + 1] ? 0xffff0000u : 0u);
-        }
-    // The epilogues are branch-free and read nothing but registers: the first version tested `v > 0` with the slope read from the kernel
+    for (int m = 0; m < MB; ++m) rmask[m] = s_in[m * 32 + li] ? 0xffffffffu : 0u;
+    // The epilogues are branch-free and read registers, the bias table and (masked form) one word of mask bits per row block: the first version tested `v > 0` with the slope read from the kernel
     // arguments inside the branch and s_in[row] from LDS per element - 32 dependent (scalar load -> wait -> multiply) chains per wave,
     // 9 k cycles per epilogue against 5 k for the conv loop in front of it (tools/trace_chain.py).  leaky(v) = max(v, slope v) for
     // 0 <= slope <= 1 (the launcher checks): the same values as the select of psnd_conv1d_cl_pair, two instructions less per element.
     // the descriptor and the bias values of pair pp + 1 are requested while pair pp runs (a scalar-cache miss and two global loads in
     // front of every first conv otherwise)
+    // An epilogue handles four channels of a row at a time (m, g): the values in the order of operations of psnd_conv1d_cl_pair (bias, mask or
+    // leaky, residual, rounding to bf16), two packed words, the row's AND mask, ONE 8-byte LDS store per tile written.
     bf16_t *prev_raw = nullptr, *prev_act = nullptr;
-    ChainPair d = p.d[0];
-    float b1 = d.bias1 ? d.bias1[col0] : 0.f, b2 = d.bias2 ? d.bias2[col0] : 0.f;
-    // BWD: v *= (M > 0 ? 1 : slope) from the bit tile `buf`: the element's byte, its bit shifted to the sign and spread, selects between
-    // v and slope * v
-    const int bsh = 31 - (col0 & 7);
-    auto masked = [&](float v, float slope, int buf, int row) __attribute__((always_inline)) {
-        const unsigned byte = sBits[buf * (MROWS * PCS) + row * PCS + (col0 >> 3)];
-        const unsigned sel = (unsigned)(((int)(byte << bsh)) >> 31);
+    auto st8 = [&](bf16_t *row0, int m, int g, unsigned w0, unsigned w1) __attribute__((always_inline)) {
+        *reinterpret_cast<uint2 *>(row0 + eo + m * 32 * RS + 8 * g) = make_uint2(w0, w1);
+    };
+    auto bias4 = [&](int buf, int conv, float4 (&bb)[4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) bb[g] = *reinterpret_cast<const float4 *>(&s_bias[buf][conv * C + cb + 8 * g]);
+    };
+    // BWD: v *= (M > 0 ? 1 : slope) from the bit tile `buf`.  One byte holds channels 8 piece ... 8 piece + 7 of a row; this wave's 32
+    // channels of row 32 m + li are the four bytes of pieces 4 wave ... 4 wave + 3 = ONE aligned 32-bit word per m, in which this lane's
+    // channel 8 g + 4 kg + j is bit 8 g + 4 kg + j.  The bit shifted to the sign and spread selects between v and slope * v.  (No bias in
+    // this form: an accumulator that starts at +0 never becomes -0, so the `+ 0.f` of a pair launch without bias changes no bit.)
+    auto mask32 = [&](int buf, int m) __attribute__((always_inline)) {
+        return *reinterpret_cast<const unsigned *>(sBits + buf * (MROWS * PCS) + (m * 32 + li) * PCS + 4 * wave) >> (4 * kg);
+    };
+    auto masked = [&](float v, float slope, unsigned bits, int j) __attribute__((always_inline)) {
+        const unsigned sel = (unsigned)(((int)(bits << (31 - j))) >> 31);
         return __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, v) & sel) | (__builtin_bit_cast(unsigned, v * slope) & ~sel));
     };
 #pragma unroll 1
     for (int pp = 0; pp < p.n_pairs; ++pp) {
         const ChainPair dn = p.d[pp + 1 < p.n_pairs ? pp + 1 : pp];
-        const float b1n = dn.bias1 ? dn.bias1[col0] : 0.f, b2n = dn.bias2 ? dn.bias2[col0] : 0.f;
+        float bn = 0.f;
+        if constexpr (!BWD) {
+            const float *bp = tid < C ? dn.bias1 : dn.bias2;
+            bn = bp ? bp[tid & (C - 1)] : 0.f;
+        }
         const float sl1 = d.act1_slope, sl2 = d.act2_slope, ms1 = d.m1_slope, ms2 = d.m2_slope;
         const __amdgpu_buffer_rsrc_t rW1 = make_uniform_rsrc(d.W1, (int)w_bytes), rW2 = make_uniform_rsrc(d.W2, (int)w_bytes);
         const __amdgpu_buffer_rsrc_t rWn = make_uniform_rsrc(dn.W1, pp + 1 < p.n_pairs ? (int)w_bytes : 0);
@@ -320,27 +355,30 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
         if constexpr (BWD) {
             // conv 2 pp reads buffer 0, conv 2 pp + 1 buffer 1
 #pragma unroll
-            for (int m = 0; m < MB; ++m)
+            for (int m = 0; m < MB; ++m) {
+                const unsigned bits = mask32(0, m);
 #pragma unroll
-                for (int q = 0; q < 16; q += 2) {
-                    const int rho = (q & 3) + 8 * (q >> 2), i = m * 32 + rho + 4 * kg;
-                    const float v0 = masked(acc[m][q] + b1, ms1, 0, i), v1 = masked(acc[m][q + 1] + b1, ms1, 0, i + 1);
-                    const unsigned w = pack_bf16(v0, v1) & mw[m][q / 2];
-                    sM[(HMAXP + i) * RS + col0] = (bf16_t)(w & 0xffffu);
-                    sM[(HMAXP + i + 1) * RS + col0] = (bf16_t)(w >> 16);
+                for (int g = 0; g < 4; ++g) {
+                    float v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = masked(acc[m][4 * g + j], ms1, bits, 8 * g + j);
+                    st8(sM + HMAXP * RS, m, g, pack_bf16(v[0], v[1]) & rmask[m], pack_bf16(v[2], v[3]) & rmask[m]);
                 }
+            }
             mask_commit(1);
         } else {
+            float4 bb[4];
+            bias4(pp & 1, 0, bb);
 #pragma unroll
             for (int m = 0; m < MB; ++m)
 #pragma unroll
-                for (int q = 0; q < 16; q += 2) {
-                    const int i = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * kg;          // rows i, i + 1
-                    const float v0 = acc[m][q] + b1, v1 = acc[m][q + 1] + b1;
-                    const unsigned w = pack_bf16(fmaxf(v0, v0 * sl1), fmaxf(v1, v1 * sl1)) & mw[m][q / 2];
-                    sM[(HMAXP + i) * RS + col0] = (bf16_t)(w & 0xffffu);
-                    sM[(HMAXP + i + 1) * RS + col0] = (bf16_t)(w >> 16);
+                for (int g = 0; g < 4; ++g) {
+                    const float v0 = acc[m][4 * g] + bb[g].x, v1 = acc[m][4 * g + 1] + bb[g].y;
+                    const float v2 = acc[m][4 * g + 2] + bb[g].z, v3 = acc[m][4 * g + 3] + bb[g].w;
+                    st8(sM + HMAXP * RS, m, g, pack_bf16(fmaxf(v0, v0 * sl1), fmaxf(v1, v1 * sl1)) & rmask[m],
+                        pack_bf16(fmaxf(v2, v2 * sl1), fmaxf(v3, v3 * sl1)) & rmask[m]);
                 }
+            s_bias[(pp + 1) & 1][tid] = bn;                  // the next pair's bias rows
         }
         if (pp == 1) CHAIN_STAMP(14);
         if constexpr (FLAGS) {
@@ -359,32 +397,42 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
         if (d.mid_out) copy_out(sM, HMAXP, d.mid_out);
         if constexpr (BWD) {
 #pragma unroll
-            for (int m = 0; m < MB; ++m)
+            for (int m = 0; m < MB; ++m) {
+                const unsigned bits = mask32(1, m);
 #pragma unroll
-                for (int q = 0; q < 16; q += 2) {
-                    const int rho = (q & 3) + 8 * (q >> 2), i = m * 32 + rho + 4 * kg;
-                    const float v0 = masked(acc[m][q] + b2, ms2, 1, i) + xres[m][q];
-                    const float v1 = masked(acc[m][q + 1] + b2, ms2, 1, i + 1) + xres[m][q + 1];
-                    const unsigned w = pack_bf16(v0, v1) & mw[m][q / 2];
-                    xres[m][q] = __builtin_bit_cast(float, w << 16), xres[m][q + 1] = __builtin_bit_cast(float, w & 0xffff0000u);
-                    sXa[(HMAXP + i) * RS + col0] = (bf16_t)(w & 0xffffu);
-                    sXa[(HMAXP + i + 1) * RS + col0] = (bf16_t)(w >> 16);
+                for (int g = 0; g < 4; ++g) {
+                    unsigned w[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int q = 4 * g + 2 * h;
+                        const float v0 = masked(acc[m][q], ms2, bits, 8 * g + 2 * h) + xres[m][q];
+                        const float v1 = masked(acc[m][q + 1], ms2, bits, 8 * g + 2 * h + 1) + xres[m][q + 1];
+                        w[h] = pack_bf16(v0, v1) & rmask[m];
+                        xres[m][q] = __builtin_bit_cast(float, w[h] << 16), xres[m][q + 1] = __builtin_bit_cast(float, w[h] & 0xffff0000u);
+                    }
+                    st8(sXa + HMAXP * RS, m, g, w[0], w[1]);
                 }
+            }
             mask_commit(0);
         } else {
+            float4 bb[4];
+            bias4(pp & 1, 1, bb);
 #pragma unroll
             for (int m = 0; m < MB; ++m)
 #pragma unroll
-                for (int q = 0; q < 16; q += 2) {
-                    const int i = m * 32 + (q & 3) + 8 * (q >> 2) + 4 * kg;
-                    const float v0 = acc[m][q] + b2 + xres[m][q], v1 = acc[m][q + 1] + b2 + xres[m][q + 1];
-                    const unsigned w = pack_bf16(v0, v1) & mw[m][q / 2];
-                    xres[m][q] = __builtin_bit_cast(float, w << 16), xres[m][q + 1] = __builtin_bit_cast(float, w & 0xffff0000u);
-                    sXr[i * RS + col0] = (bf16_t)(w & 0xffffu);
-                    sXr[(i + 1) * RS + col0] = (bf16_t)(w >> 16);
-                    const unsigned wa = pack_bf16(fmaxf(v0, v0 * sl2), fmaxf(v1, v1 * sl2)) & mw[m][q / 2];
-                    sXa[(HMAXP + i) * RS + col0] = (bf16_t)(wa & 0xffffu);
-                    sXa[(HMAXP + i + 1) * RS + col0] = (bf16_t)(wa >> 16);
+                for (int g = 0; g < 4; ++g) {
+                    const float bq[4] = {bb[g].x, bb[g].y, bb[g].z, bb[g].w};
+                    unsigned w[2], wa[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int q = 4 * g + 2 * h;
+                        const float v0 = acc[m][q] + bq[2 * h] + xres[m][q], v1 = acc[m][q + 1] + bq[2 * h + 1] + xres[m][q + 1];
+                        w[h] = pack_bf16(v0, v1) & rmask[m];
+                        xres[m][q] = __builtin_bit_cast(float, w[h] << 16), xres[m][q + 1] = __builtin_bit_cast(float, w[h] & 0xffff0000u);
+                        wa[h] = pack_bf16(fmaxf(v0, v0 * sl2), fmaxf(v1, v1 * sl2)) & rmask[m];
+                    }
+                    st8(sXr, m, g, w[0], w[1]);
+                    st8(sXa + HMAXP * RS, m, g, wa[0], wa[1]);
                 }
         }
         if (pp == 1) CHAIN_STAMP(15);
@@ -396,7 +444,7 @@ __global__ __launch_bounds__(512, 1) void conv_chain_kernel(ChainParams p) {
         }
         CHAIN_STAMP(5 + 4 * pp);
         prev_raw = d.out_raw, prev_act = d.out_act;
-        d = dn, b1 = b1n, b2 = b2n;
+        d = dn;
     }
     if constexpr (FLAGS) __syncthreads();                  // every wave's last epilogue is in the tiles
     if (prev_raw) copy_out(BWD ? sXa : sXr, BWD ? HMAXP : 0, prev_raw);
@@ -449,8 +497,8 @@ extern "C" int psnd_conv1d_cl_chain(const void *A, const void *res, const psnd_c
         if (!pairs[i].W1 || !pairs[i].W2) PSND_FAIL(PSND_E_ARG, "conv1d_cl_chain: pair %d without weights", i);
         if (bwd != (pairs[i].M1 != nullptr) || bwd != (pairs[i].M2 != nullptr))
             PSND_FAIL(PSND_E_ARG, "conv1d_cl_chain: pair %d: masks on every conv of the chain (the input-gradient form) or on none", i);
-        if (bwd && (res != A || pairs[i].act1_slope != 1.f || pairs[i].act2_slope != 1.f || pairs[i].out_act))
-            PSND_FAIL(PSND_E_UNSUPPORTED, "conv1d_cl_chain: pair %d: the masked (input-gradient) form has res == A, no activation, no out_act", i);
+        if (bwd && (res != A || pairs[i].act1_slope != 1.f || pairs[i].act2_slope != 1.f || pairs[i].out_act || pairs[i].bias1 || pairs[i].bias2))
+            PSND_FAIL(PSND_E_UNSUPPORTED, "conv1d_cl_chain: pair %d: the masked (input-gradient) form has res == A, no activation, no bias, no out_act", i);
         if (!(pairs[i].act1_slope >= 0.f && pairs[i].act1_slope <= 1.f && pairs[i].act2_slope >= 0.f && pairs[i].act2_slope <= 1.f))
             PSND_FAIL(PSND_E_UNSUPPORTED, "conv1d_cl_chain: activation slopes %g, %g of pair %d outside [0, 1]", pairs[i].act1_slope, pairs[i].act2_slope, i);
     }
