@@ -22,6 +22,7 @@
 #include "psnd_conv_pair.h"
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 
 namespace {
@@ -1090,31 +1091,48 @@ __global__ __launch_bounds__(256, 2) void conv_pair_bwd_kernel(pairk::PairParams
     }
 }
 
-// The weight gradients of MANY convs of one shape in one launch (psnd_conv1d_cl_wgrad_multi): workgroup b takes tile / row range
-// b % per_conv of conv b / per_conv.  For the batched backward of a conv chain (cl.py): the input-gradient chain runs first, alone,
-// and every weight gradient it left behind is computed here at full occupancy instead of riding along in 12 latency-bound launches.
+// The weight gradients of MANY convs in one launch (psnd_conv1d_cl_wgrad_multi).  For the batched backward of a conv chain (cl.py): the
+// input-gradient chain runs first, alone, and every weight gradient it left behind is computed here at full occupancy instead of riding
+// along in 12 latency-bound launches.
+// Which workgroup takes which tile decides what the launch waits for.  The 16 tiles (wgx * wgy * tap groups) of one conv over one row
+// range - a GROUP - read the same rows of g and xa, a quarter of the channels each: a group that sits behind ONE L2 fetches every row once
+// and reads it 4 x from there, a group dealt over the eight L2s fetches it into each.  Workgroups are dispatched round-robin over the 8
+// XCDs (b and b + 8 share an L2), so the launch numbers them label-first: label = b % 8, t = b / 8 walks the tiles of the label's groups
+// one group after the other, and the first 8 T workgroups dispatched are 8 whole groups.  Row range s of conv c sits on label
+// (lab0[c] + s) % 8; the host picks lab0 so that the labels carry even loads (heaviest convs first) and pads the grid to 8 x the heaviest
+// label - a workgroup past its label's last tile returns at once.  The label is used for speed only: any placement gives the same slabs.
+// linear (lab builds, PSND_WGRAD_MULTI_MAP=linear): the numbering of before, conv after conv, for same-box A/B timings.
 constexpr int WGRAD_MULTI_MAX = 32;
 struct WgradMultiArgs {
     WgradParams base;
-    int n;
-    int blk0[WGRAD_MULTI_MAX + 1];      // first workgroup of conv i
+    int n, linear, ci_fastest;
     struct {
         const bf16_t *g, *xa;
         float *gw, *gb;
-        int off0, dstep, Ca, Cb, k, rps, wgx, wgy;
+        int off0, dstep, Ca, Cb, k, rps, wgx, wgy, splits, tiles, lab0;     // tiles: workgroups per row range = wgx * wgy * tap groups
     } c[WGRAD_MULTI_MAX];
 };
 __global__ __launch_bounds__(256, 2) void conv_wgrad_multi_kernel(WgradMultiArgs a) {
     extern __shared__ __attribute__((aligned(16))) bf16_t smem_dyn[];
-    int c = 0;
-    while (c + 1 < a.n && (int)blockIdx.x >= a.blk0[c + 1]) ++c;          // uniform
-    const int b = (int)blockIdx.x - a.blk0[c];
+    const bool lin = a.linear != 0;
+    const int label = lin ? 0 : (int)(blockIdx.x & 7), sh = lin ? 0 : 3;
+    int t = (int)blockIdx.x >> sh, c = 0, split = 0;
+    for (; c < a.n; ++c) {                                               // uniform: the label's row ranges of conv c are first, first + 8, ..
+        const int first = lin ? 0 : (label - a.c[c].lab0) & 7, S = a.c[c].splits, T = a.c[c].tiles;
+        const int nb = first < S ? (((S - first - 1) >> sh) + 1) * T : 0;
+        if (t < nb) {
+            split = first + ((t / T) << sh), t = t % T;
+            break;
+        }
+        t -= nb;
+    }
+    if (c == a.n) return;                                                // grid padding of a lighter label (before any barrier)
     WgradParams w = a.base;
     w.G1 = a.c[c].g, w.xa = a.c[c].xa, w.gw = a.c[c].gw, w.gbias = a.c[c].gb, w.off0 = a.c[c].off0, w.dstep = a.c[c].dstep;
     w.Ca = a.c[c].Ca, w.Cb = a.c[c].Cb, w.k = a.c[c].k, w.rows_per_split = a.c[c].rps;
-    const int wgx = a.c[c].wgx, wgy = a.c[c].wgy;
-    const int bx = b % wgx, r = b / wgx;
-    conv_wgrad_body<false>(w, bx, r % wgy, r / wgy, smem_dyn, 0);
+    const int wgx = a.c[c].wgx, wgy = a.c[c].wgy, txy = t % (wgx * wgy), tgrp = t / (wgx * wgy);
+    const int bx = a.ci_fastest ? txy / wgy : txy % wgx, by = a.ci_fastest ? txy % wgy : txy / wgx;
+    conv_wgrad_body<false>(w, bx, by, split * (a.c[c].tiles / (wgx * wgy)) + tgrp, smem_dyn, 0);
 }
 
 // ---- weight prep: weight norm (dim 0) + both bf16 packs + padded bias, one block per output channel ------
@@ -1828,7 +1846,6 @@ extern "C" int psnd_conv1d_cl_wgrad_multi(const psnd_wgrad_desc *d, int n, int64
     wgrad_params_plain(a.base);
     a.base.G2 = nullptr, a.base.GM = nullptr, a.base.g_out = nullptr, a.base.R = R, a.base.g2_slope = 1.f;
     a.n = n;
-    int total = 0;
     for (int i = 0; i < n; ++i) {
         const int Ca = d[i].Ca, Cb = d[i].Cb, k = d[i].k, splits = d[i].splits;
         if (!d[i].g || !d[i].xa || !d[i].gw_part) PSND_FAIL(PSND_E_ARG, "conv1d_cl_wgrad_multi: conv %d: null pointer", i);
@@ -1845,11 +1862,39 @@ extern "C" int psnd_conv1d_cl_wgrad_multi(const psnd_wgrad_desc *d, int n, int64
         a.c[i].g = static_cast<const bf16_t *>(d[i].g), a.c[i].xa = static_cast<const bf16_t *>(d[i].xa);
         a.c[i].gw = d[i].gw_part, a.c[i].gb = d[i].gbias_part, a.c[i].off0 = d[i].off0, a.c[i].dstep = d[i].dstep;
         a.c[i].Ca = Ca, a.c[i].Cb = Cb, a.c[i].k = k, a.c[i].rps = (int)rps;
-        a.c[i].wgx = (Cb + 63) / 64, a.c[i].wgy = (Ca + 63) / 64;
-        a.blk0[i] = total;
-        total += a.c[i].wgx * a.c[i].wgy * splits * ((k + WKT - 1) / WKT);
+        a.c[i].wgx = (Cb + 63) / 64, a.c[i].wgy = (Ca + 63) / 64, a.c[i].splits = splits;
+        a.c[i].tiles = a.c[i].wgx * a.c[i].wgy * ((k + WKT - 1) / WKT);
     }
-    a.blk0[n] = total;
+    if (const char *e = PSND_ENV("PSND_WGRAD_MULTI_MAP")) a.linear = !strcmp(e, "linear");            // A/B: conv after conv, as before
+    if (const char *e = PSND_ENV("PSND_WGRAD_MULTI_ORDER")) a.ci_fastest = !strcmp(e, "ci");          // A/B: tile order inside a group
+    // labels (see conv_wgrad_multi_kernel): the heaviest convs first, each starts its row ranges on the label that leaves the heaviest
+    // label lightest (then the smallest sum of squares: the evenest spread)
+    int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0}, total = 0;
+    int order[WGRAD_MULTI_MAX];
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order, order + n, [&](int x, int y) { return a.c[x].tiles > a.c[y].tiles; });
+    for (int oi = 0; oi < n; ++oi) {
+        const int i = order[oi], S = a.c[i].splits;
+        int best = 0;
+        int64_t best_max = -1, best_sq = 0;
+        for (int o = 0; o < 8 && !a.linear; ++o) {
+            int64_t mx = 0, sq = 0;
+            for (int l = 0; l < 8; ++l) {
+                const int first = (l - o) & 7;
+                const int64_t v = load[l] + (first < S ? (int64_t)((S - first - 1) / 8 + 1) * a.c[i].tiles : 0);
+                mx = v > mx ? v : mx, sq += v * v;
+            }
+            if (best_max < 0 || mx < best_max || (mx == best_max && sq < best_sq)) best = o, best_max = mx, best_sq = sq;
+        }
+        a.c[i].lab0 = best;
+        for (int l = 0; l < 8; ++l) {
+            const int first = (l - best) & 7;
+            if (first < S) load[l] += (int64_t)((S - first - 1) / 8 + 1) * a.c[i].tiles;
+        }
+        total += (int64_t)S * a.c[i].tiles;
+    }
+    if (!a.linear) total = 8 * *std::max_element(load, load + 8);
+    if (total > 0x7fffffff) PSND_FAIL(PSND_E_SHAPE, "conv1d_cl_wgrad_multi: %lld workgroups", (long long)total);
     hipLaunchKernelGGL(conv_wgrad_multi_kernel, dim3((unsigned)total), dim3(256), kWgradLdsBytes, static_cast<hipStream_t>(stream), a);
     PSND_CHECK_LAUNCH("conv1d_cl_wgrad_multi");
     return PSND_OK;
