@@ -139,13 +139,15 @@ def test_config4_block_vs_float64(T, N):
         for m in (mha, ffn) + ref_mods[1:]:
             m.zero_grad()
         y, att, gx, gp = run((pe, mha, ffn), torch.float32, att_in_loss)
-        yr, attr, gxr, gpr = run(ref_mods, torch.float64, att_in_loss)
         # yardstick: the SAME formulation in plain fp32 torch ops (library GEMMs, torch softmax / group_norm) against float64 -
         # what fp32 arithmetic itself costs at this size (the softmax backward cancels: att * (g - sum att g))
         import pytorch_sound_amd.models.modules as M
         keep_hip_ok = M._hip_ok
-        M._hip_ok = lambda t: False                   # the torch formulation evaluated on the GPU: this test's fp32 yardstick
+        M._hip_ok = lambda t: False                   # the torch formulation evaluated on the GPU: the float64 reference and this test's fp32 yardstick
         try:
+            # (the float64 run too: a float64 HIP tensor handed to the modules is cast to fp32 and takes the kernels - that is no reference)
+            yr, attr, gxr, gpr = run(ref_mods, torch.float64, att_in_loss)
+            assert yr.dtype == torch.float64 and all(v.dtype == torch.float64 for v in gpr.values())
             for m in (mha, ffn):
                 m.zero_grad()
             y32, att32, gx32, gp32 = run((pe, mha, ffn), torch.float32, att_in_loss)
