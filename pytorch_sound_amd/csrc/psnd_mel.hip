@@ -111,9 +111,7 @@ __device__ __forceinline__ f32x4 load_b_raw(__amdgpu_buffer_rsrc_t r, int c, int
 }
 
 // NFK: the magnitude side of the product is bin-fastest, (N, F, K) (psnd_stft_mag_nfk) - forward: the INPUT, backward: the OUTPUT.
-//   forward   a lane loads 16 B = 4 consecutive BINS 16 S + 4 kk .. + 3 of ONE frame (f + g for accumulator g); component j feeds the MFMA
-//             whose A operand holds W[.][16 S + 4 kk + j] (a second weight table in 16-bin groups, plan[wn_off ..)): the same 16 MFMAs
-//             per 16 bins and 4 loads of 16 B as the frame-fastest walk.  The last group of a row (K = 513: one bin) takes element loads.
+//   forward   mel_fwd_nfk_kernel (below)
 //   backward  a lane owns 4 consecutive bins of a frame per accumulator: one 16-byte store each.
 template <bool BWD, bool NFK = false>
 __global__ __launch_bounds__(256) void mel_kernel(MelParams p) {
@@ -137,52 +135,11 @@ __global__ __launch_bounds__(256) void mel_kernel(MelParams p) {
     const float l1c = l1b ? p.l1_coef * p.l1_g[0] : 0.f;
 
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
-    // the band is walked in batches of MU k-steps with all loads of a batch in flight
-#ifndef PSND_MEL_MU
-#define PSND_MEL_MU 8
-#endif
-    constexpr int MU = PSND_MEL_MU;
-    if constexpr (!BWD && NFK) {
-        const int K = p.Cc;
-        const f32x4 *Wn = reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(p.plan) + p.wn_off) + (size_t)rt * p.CS16 * 64 + lane;
-        const int lo16 = lo >> 2, hi16 = (hi + 3) >> 2;
-        constexpr unsigned OOB = 0xffffffffu;
-        // byte offset of bin 4 kk of frame f + g inside the clip, or out of range for a frame past the clip
-        unsigned fb[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) fb[g] = (f + g < F) ? (unsigned)((((size_t)(f + g)) * K + 4 * kk) * sizeof(float)) : OOB;
-        for (int S0 = lo16; S0 < hi16; S0 += 2) {
-            f32x4 a[2], b[2][4];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int S = S0 + u;
-                const bool in = S < hi16;
-                a[u] = in ? Wn[(size_t)S * 64] : f32x4{0.f, 0.f, 0.f, 0.f};
-                if (16 * S + 16 <= K || !in) {                                  // (uniform) whole group inside the row
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        b[u][g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r0, (int)((in && fb[g] != OOB) ? fb[g] + 64u * (unsigned)S : OOB), 0, 0));
-                } else {                                                        // the row ends inside the group: element by element
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            b[u][g][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                r0, (int)((fb[g] != OOB && 16 * S + 4 * kk + j < K) ? fb[g] + 64u * (unsigned)S + 4u * j : OOB), 0, 0));
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][0][j], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][1][j], acc1, 0, 0, 0);
-                    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][2][j], acc2, 0, 0, 0);
-                    acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][3][j], acc3, 0, 0, 0);
-                }
-        }
-    } else
-    for (int s0 = lo; s0 < hi; s0 += MU) {
+    // One batch of MU k-steps from s0, all its loads in flight.  In the backward every slot of a batch costs two loads and four gradient
+    // factors (a logf, a division and the clamp compares each) per lane whether the band reaches it or not, and the triangles of a mel
+    // filter bank give a 16-bin tile 1 - 3 steps: the batch is sized to what is left of the band (below).
+    auto batch = [&](auto muc, int s0) __attribute__((always_inline)) {
+        constexpr int MU = decltype(muc)::value;
         float a[MU];
         f32x4 b[MU], m[BWD ? MU : 1];
 #pragma unroll
@@ -217,6 +174,24 @@ __global__ __launch_bounds__(256) void mel_kernel(MelParams p) {
             acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u].z, acc2, 0, 0, 0);
             acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u].w, acc3, 0, 0, 0);
         }
+    };
+#ifndef PSND_MEL_MU
+#define PSND_MEL_MU 8
+#endif
+    // Backward: whole batches of 4, then an instance of exactly the 1 .. 3 steps that are left (wave-uniform branch) - all of the band for
+    // a mel filter bank, nothing for a tile above fmax, which only stores its zeros.  The MFMAs are those of the steps inside the band,
+    // in ascending order, whatever the batching.  4 and not 8: the operands of 8 steps cost 139 + 40 registers = 2 waves per SIMD for the
+    // 3 that a 32-clip launch brings; with 73 + 40 all are resident at once, and a dense matrix (20 steps) is faster as well.
+    constexpr int MU = BWD ? 4 : PSND_MEL_MU;
+    int s0 = lo;
+    for (; s0 + MU <= hi; s0 += MU) batch(std::integral_constant<int, MU>{}, s0);
+    if constexpr (BWD) {
+        const int rest = hi - s0;
+        if (rest == 1) batch(std::integral_constant<int, 1>{}, s0);
+        else if (rest == 2) batch(std::integral_constant<int, 2>{}, s0);
+        else if (rest == 3) batch(std::integral_constant<int, 3>{}, s0);
+    } else {
+        if (s0 < hi) batch(std::integral_constant<int, MU>{}, s0);      // padded: a slot past the band multiplies zeros
     }
     // D layout: col = lane&15 (-> frames f..f+3 across acc0..3), row = 4*(lane>>4) + reg
     const size_t obase = (size_t)clip * p.R * F;
@@ -285,6 +260,121 @@ __global__ __launch_bounds__(256) void mel_kernel(MelParams p) {
             for (int m = 32; m >= 1; m >>= 1) d += __shfl_xor(d, m, 64);
             if (lane == 0) p.l1_part[wid] = d;
         }
+    }
+}
+
+// ---- forward on a bin-fastest magnitude, (N, F, K) ----------------------------------------------------------------------------------------
+// A lane loads 16 B = 4 consecutive BINS 16 S + 4 kk .. + 3 of ONE frame; component j feeds the MFMA whose A operand holds
+// W[.][16 S + 4 kk + j] (the weight table in 16-bin groups, plan[wn_off ..)).  The last group of a row (K = 513: one bin) takes element
+// loads.  One wave = (clip, 16 frames, 16 mel bands) with ONE accumulator (output column = frame); the four waves of a workgroup are the
+// four 16-frame tiles of a (clip, 64 frames, 16 mel bands) unit and fold their L1 partial sums into that unit's slot, so the slots are
+// those of mel_kernel.  (The first version gave a wave 64 frames: 480 waves for 1024 SIMDs at 32 clips x 173 frames x 80 bands, the
+// widest band tile of the 0 - 8 kHz filter walked 12 groups two at a time - six memory latencies and 192 MFMAs in a row on a SIMD that
+// held nothing else - next to idle SIMDs and to waves with 2 groups.  MFMA output columns are independent, so regrouping the frames
+// leaves every sum as it was: the 16-bin groups of the band in ascending order, j = 0 .. 3 inside a group.)
+// Workgroups are numbered with the LAST band tile first (the triangles widen with frequency: the longest waves start first), and the
+// operands of kNfkRing groups are in flight ahead of the MFMAs through a register ring: loop-carried and branch-free, a group past the
+// band or a frame past the clip reads zeros through the descriptor's range check and is never multiplied.
+constexpr int kNfkRing = 6;
+
+__global__ __launch_bounds__(256) void mel_fwd_nfk_kernel(MelParams p) {
+    __shared__ double l1s[4];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long per_rt = (long long)p.N * p.nft;
+    const int rt = p.RT - 1 - (int)(blockIdx.x / per_rt);
+    const long long cf = blockIdx.x % per_rt;
+    const int clip = (int)(cf / p.nft), ft = (int)(cf - (long long)clip * p.nft);
+    const long long F = p.F;
+    const long long f0 = (long long)ft * 64 + 16 * w;        // first frame of the wave
+    const long long fr = f0 + (lane & 15);                   // the lane's frame: B column and D column
+    const int kk = lane >> 4;
+    const int K = p.Cc;
+    constexpr unsigned OOB = 0xffffffffu;
+    constexpr int D = kNfkRing;
+
+    // the band in 16-bin groups [lo16, hi16): whole groups [lo16, hiF), then the group the row ends in, if the band reaches it
+    int lo16 = p.plan[p.band_off + 2 * rt] >> 2, hi16 = (p.plan[p.band_off + 2 * rt + 1] + 3) >> 2;
+    if (f0 >= F) lo16 = hi16 = 0;                            // (uniform) a wave past the clip only takes part in the fold of the partials
+    const bool part = hi16 > lo16 && 16 * hi16 > K;
+    const int hiF = part ? hi16 - 1 : hi16;
+    const f32x4 *Wn = reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(p.plan) + p.wn_off) + (size_t)rt * p.CS16 * 64 + lane;
+    const __amdgpu_buffer_rsrc_t r0 = make_uniform_rsrc(p.in0 + (size_t)clip * K * F, (int)((size_t)K * F * sizeof(float)));
+    // byte offset of bin 4 kk of the lane's frame inside the clip, or out of range for a frame past the clip
+    const unsigned fb = fr < F ? (unsigned)((((size_t)fr) * K + 4 * kk) * sizeof(float)) : OOB;
+
+    // Loads complete in the order of their issue, so the oldest are the ones wanted last: the L1 targets of the epilogue (zeros without a
+    // target: an empty descriptor), then the group the row ends in, element by element (zeros for a band that ends before it), then the ring.
+    const size_t obase = (size_t)clip * p.R * F;
+    const __amdgpu_buffer_rsrc_t rr = make_uniform_rsrc(p.l1_ref ? p.l1_ref + obase : p.in0, p.l1_ref ? (int)((size_t)p.R * F * sizeof(float)) : 0);
+    float rf[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = 16 * rt + 4 * kk + r;
+        rf[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+            rr, (int)((row < p.R && fr < F) ? (unsigned)(((size_t)row * F + fr) * sizeof(float)) : OOB), 0, 0));
+    }
+    const int SL = max(hi16 - 1, 0);
+    const f32x4 al = Wn[(size_t)SL * 64];
+    f32x4 bl;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        bl[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+            r0, (int)((part && fb != OOB && 16 * SL + 4 * kk + j < K) ? fb + 64u * (unsigned)SL + 4u * j : OOB), 0, 0));
+    f32x4 ra[D], rb[D];
+    auto load = [&](int S, f32x4 &a, f32x4 &b) __attribute__((always_inline)) {
+        a = Wn[(size_t)max(min(S, hiF - 1), 0) * 64];                           // a group past the band: any table entry, not used
+        b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r0, (int)((S < hiF && fb != OOB) ? fb + 64u * (unsigned)S : OOB), 0, 0));
+    };
+#pragma unroll
+    for (int u = 0; u < D; ++u) load(lo16 + u, ra[u], rb[u]);
+    __builtin_amdgcn_sched_barrier(0);
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int S = lo16;
+    for (; S + D <= hiF; S += D) {
+#pragma unroll
+        for (int u = 0; u < D; ++u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ra[u][j], rb[u][j], acc, 0, 0, 0);
+            load(S + D + u, ra[u], rb[u]);                                      // into the registers just read: no copy, no wait at the loop end
+            __builtin_amdgcn_sched_barrier(0);                                  // refills stay in slot order: the wait of slot u leaves D - 1 in flight
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < D - 1; ++u)
+        if (S + u < hiF) {                                                      // (uniform) what is left of the ring
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ra[u][j], rb[u][j], acc, 0, 0, 0);
+        }
+    if (part) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(al[j], bl[j], acc, 0, 0, 0);
+    }
+
+    // D layout: col = lane&15 (-> frame fr), row = 4*(lane>>4) + reg: 16 lanes write 16 consecutive frames of a mel row
+    double l1acc = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = 16 * rt + 4 * kk + r;
+        if (row >= p.R || fr >= F) continue;
+        const float v = acc[r];
+        const float y = fminf(fmaxf(log_apply(v, p.log_kind, p.log_offset, p.pre_clamp_min), p.clamp_lo), p.clamp_hi);
+        const size_t o = obase + (size_t)row * F + fr;
+        if (p.l1_ref) {                                                         // fused L1 against ref: the log-mel itself is not written
+            l1acc += (double)fabsf(y - rf[r]);
+            p.lin[o] = v;
+            continue;
+        }
+        p.out[o] = y;
+        if (p.lin) p.lin[o] = v;
+    }
+    if (p.l1_part) {                          // one partial sum per workgroup, in mel_kernel's order: (clip, 64-frame tile, mel tile)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) l1acc += __shfl_xor(l1acc, m, 64);
+        if (lane == 0) l1s[w] = l1acc;
+        __syncthreads();
+        if (threadIdx.x == 0) p.l1_part[((long long)clip * p.nft + ft) * p.RT + rt] = (l1s[0] + l1s[1]) + (l1s[2] + l1s[3]);
     }
 }
 
@@ -531,10 +621,11 @@ static int mel_launch(bool bwd, const float *in0, const float *in1, int64_t N, i
     const bool once = !bwd && !nfk && h.MT <= kOnceTiles;          // forward on (N, K, F): every magnitude read once
     const long long waves = (long long)N * p.nft * p.RT;
     const long long blocks = (waves + 3) / 4;
-    if (blocks >= (1ll << 31)) PSND_FAIL(PSND_E_SHAPE, "mel: grid too large");
+    if (blocks >= (1ll << 31) || waves >= (1ll << 31)) PSND_FAIL(PSND_E_SHAPE, "mel: grid too large");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (nfk) {
-        if (!bwd) hipLaunchKernelGGL((mel_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        // forward: one workgroup per (mel tile, clip, 64-frame tile), i.e. per wave of mel_kernel's numbering
+        if (!bwd) hipLaunchKernelGGL(mel_fwd_nfk_kernel, dim3((unsigned)waves), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((mel_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     } else if (!bwd && once) {
         const long long ob = ((long long)N * p.nft + 3) / 4;
@@ -583,7 +674,8 @@ extern "C" int psnd_mel_l1_bwd(const float *ref, const float *mel_lin, const flo
 }
 
 // ---- the same four with the magnitude side bin-fastest, (N, F, K) (psnd_stft_mag_nfk): forward INPUT mag_nfk, backward OUTPUT gmag_nfk; the
-//      mel side stays (N, M, F) as transforms.py:235 returns it.
+//      mel side stays (N, M, F) as transforms.py:235 returns it.  psnd_mel_l1_fwd_nfk writes the same psnd_mel_l1_blocks partial sums, one
+//      per (clip, 64 frames, 16 mel bands): there a workgroup's, summed in double from the first term on.
 extern "C" int psnd_mel_fwd_nfk(const float *mag_nfk, int64_t N, int64_t F, int M, int K, const void *mel_plan, int log_kind, float log_offset,
                                 float pre_clamp_min, float clamp_lo, float clamp_hi, float *out, float *mel_lin, void *stream) {
     return mel_launch(false, mag_nfk, nullptr, N, F, M, K, mel_plan, log_kind, log_offset, pre_clamp_min, clamp_lo, clamp_hi, out, mel_lin, stream,
