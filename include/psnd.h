@@ -380,7 +380,10 @@ int psnd_cl_colsum(const void *g, int64_t rows, int C, int Lp, int lo, int hi, f
  *   groups are not written (zero them once). */
 int psnd_conv1d_prep_multi(const void *descs_dev, int n, int total_blocks, int max_row, int which, void *stream);
 /* psnd_conv1d_wnorm_bwd for up to PSND_WNORM_MAX convs (the six of a ResBlock1, the 26 of the separator body) in one launch; descs is a HOST array,
- * passed to the kernel by value (nothing is uploaded, the launch can be captured in a hipGraph). */
+ * passed to the kernel by value (nothing is uploaded, the launch can be captured in a hipGraph).  A launch whose rows all have Cin k < 2048 and
+ * at most 16 slabs runs 256 threads; there a conv with Cin and Ca multiples of 4 takes one workgroup per EIGHT output channels (every load in
+ * flight before the first wait, v read once), any other conv of the launch one workgroup per channel.  The sums are grouped as in the
+ * one-channel form: the same bits either way, as from psnd_conv1d_wnorm_bwd. */
 #define PSND_WNORM_MAX 32
 typedef struct psnd_wnorm_desc {
     const float *gw_part, *gbias_part;      /* slabs of psnd_conv1d_cl_wgrad / psnd_conv1d_cl_bwd (gbias_part may be NULL) */

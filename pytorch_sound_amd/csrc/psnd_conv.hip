@@ -1459,12 +1459,235 @@ __device__ __forceinline__ void conv_finish_body(const float *gw_part, const flo
     }
 }
 
-template <bool MANY>
-__global__ __launch_bounds__(1024) void conv_finish_kernel(const float *gw_part, const float *gb_part, int splits, const float *v,
-                                                           const float *g, int Cout, int Cin, int k, int Cb, int Ca, float *gv,
-                                                           float *gg, float *gbias, unsigned kmagic, unsigned cmagic) {
+// ---- the lean form of a 256-thread launch: FIN_ROWS output channels per workgroup, one memory round trip --------------------
+// One channel per workgroup asked for 12 KB at a time and waited for it three times over (slabs, v, v again; 6913 workgroups of 192 busy
+// threads at config 2: 35 us for 76 MB of cache-resident traffic).  Here a workgroup owns FIN_ROWS consecutive channels of one conv and
+// issues every load it needs - the slab quads, the v quads (kept in registers up to the g_v store), the bias slab values, g - before it
+// waits for the first (with two slabs; more slabs come in batches of 16 loads per thread behind the first, for the registers).
+// The sums keep the grouping of the one-channel form, so the results are the same bits: the 256 threads of the old workgroup are four
+// VIRTUAL waves per channel (virtual thread t = 64 vw + lane owns the quads q = t, t + 256 in ONE fma chain, a virtual wave ends in a
+// 64-lane butterfly, the four wave sums - zeros of idle waves included - are added in order).  Real wave w plays the 4 virtual waves of
+// channels 2 w and 2 w + 1, one after the other in the same lanes.  Channels past Cout and virtual waves past the row are skipped
+// wave-uniformly; every wave reaches both barriers.
+constexpr int FIN_ROWS = 8;
+constexpr size_t FIN_ROWS_LDS_MAX = 64 * 1024;        // the 8-row tile [row][j][Cin + 1]; larger rows keep the one-channel form
+// (the 256-thread launches run rows of n = Cin k < 2048: at most two quads per virtual thread.  Two quads with 16 slab slots do not fit 128
+//  registers - the v quads of 16 units and one unit's slab quads - and keep the one-channel form as well.)
+__host__ __device__ inline bool conv_finish_in_rows(int Cin, int k, int Cb, int Ca, int splits) {
+    return (Cin & 3) == 0 && (Ca & 3) == 0 && splits <= 16 && Cin * k < 2048 && (splits <= 8 || Cin * k <= 1024) &&
+           sizeof(float) * FIN_ROWS * (size_t)(Cin + 1) * (size_t)k <= FIN_ROWS_LDS_MAX && (size_t)k * Cb * Ca * (size_t)splits < ((size_t)1 << 29);
+}
+
+// four workgroups of the 256-thread launch per CU (one wave of each per SIMD): 128 registers
+#define FIN_WAVES(BD) ((BD) == 256 ? 4 : 1)
+
+// x of lane ^ M, all 64 lanes active: what __shfl_xor(x, M, 64) returns, without its five index instructions and its LDS address per call
+// (18 butterflies of six steps per wave below) - DPP within a row of 16 lanes, ds_swizzle (no address) within 32
+template <int M>
+__device__ __forceinline__ float fin_lane_xor(float x) {
+    const int i = __builtin_bit_cast(int, x);
+    if constexpr (M == 1) return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(i, 0xB1, 0xF, 0xF, true));         // quad_perm [1,0,3,2]
+    else if constexpr (M == 2) return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(i, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+    else if constexpr (M == 8) return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(i, 0x128, 0xF, 0xF, true));   // row_ror:8
+    else if constexpr (M == 4 || M == 16) return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(i, (M << 10) | 0x1F));
+    else return __shfl_xor(x, M, 64);
+}
+// the butterfly of the one-channel form, m = 32 ... 1: x += x of lane ^ m (the same pairs meet in the same order)
+__device__ __forceinline__ float fin_butterfly(float x) {
+    x += fin_lane_xor<32>(x);
+    x += fin_lane_xor<16>(x);
+    x += fin_lane_xor<8>(x);
+    x += fin_lane_xor<4>(x);
+    x += fin_lane_xor<2>(x);
+    x += fin_lane_xor<1>(x);
+    return x;
+}
+
+template <int NS, int P>   // NS slab slots (slots past `splits` re-read the last slab and add zero), P quads per virtual thread
+__device__ __forceinline__ void conv_finish_rows(const float *gw_part, const float *gb_part, int splits, const float *v, const float *g,
+                                                 int Cout, int Cin, int k, int Cb, int Ca, float *gv, float *gg, float *gbias,
+                                                 unsigned kmagic, unsigned c4magic, const int co0, float *s_gw, float *red) {
+    constexpr int RW = FIN_ROWS / 4, NU = RW * 4 * P;                // channels per real wave, (channel, virtual wave, quad) units per thread
+    constexpr int UB = 16 / P >= NS ? 16 / P / NS : 1;               // units per batch of slab loads: 16 / P 16-byte loads in flight on top of v
+    static_assert(NU % UB == 0, "slab batches");
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = Cin * k, n4 = n >> 2, cin4 = Cin >> 2, pitch = Cin + 1;       // q / cin4 by c4magic = ceil(2^32 / cin4), q < 512
+    const unsigned slab_bytes = (unsigned)k * Cb * Ca * 4u;                     // (below 2^31 with every slab: conv_finish_in_rows)
+    const bool bias = gbias && gb_part;
+    // Buffer loads and stores: a lane with nothing to do (past the row, past Cout, a slab slot past `splits`) passes an offset outside the
+    // buffer, which reads zero and touches no memory - the loads stand in straight-line code, none behind a branch.
+    constexpr unsigned OUTSIDE = 0x80000000u;
+    const __amdgpu_buffer_rsrc_t r_gw = make_uniform_rsrc(gw_part, (int)(slab_bytes * (unsigned)splits));
+    const __amdgpu_buffer_rsrc_t r_v = make_uniform_rsrc(v, Cout * n * 4), r_gv = make_uniform_rsrc(gv, Cout * n * 4);
+    const __amdgpu_buffer_rsrc_t r_g = make_uniform_rsrc(g, Cout * 4), r_gb = make_uniform_rsrc(gb_part, bias ? splits * Cb * 4 : 0);
+    // unit u = (rr * 4 + vw) * P + p: channel co0 + RW w + rr, quad 64 vw + lane + 256 p
+    auto unit_co = [&](int u) { return co0 + RW * w + u / (4 * P); };
+    auto unit_q0 = [&](int u) { return 64 * ((u / P) & 3) + 256 * (u % P); };
+    auto unit_live = [&](int u) { return unit_co(u) < Cout && unit_q0(u) < n4; };                 // (uniform)
+    // the lane number anew for every phase: what one phase works out from it (LDS addresses, four per quad) is not carried in registers
+    // to the next
+    auto fresh = [](int x) __attribute__((always_inline)) {
+        asm volatile("" : "+v"(x));
+        return x;
+    };
+    // the LDS places j * pitch + ci of the four elements i = 4 q + e of a quad in natural (ci, j) order: one division for the quad, then a
+    // step of one tap with a wrap into the next channel (32-bit integer multiplies run at a quarter of the rate)
+    const int tap_wrap = 1 - (k - 1) * pitch;
+    auto quad_places = [&](int q, int (&at)[4]) __attribute__((always_inline)) {
+        const int ci = (int)__umulhi((unsigned)(4 * q), kmagic);
+        int j = 4 * q - ci * k;
+        at[0] = j * pitch + ci;
+#pragma unroll
+        for (int e = 1; e < 4; ++e) {
+            const bool wrap = ++j == k;
+            j = wrap ? 0 : j;
+            at[e] = at[e - 1] + (wrap ? tap_wrap : pitch);
+        }
+    };
+    // tap of quad q in (j, ci) order, q / cin4 (one quad per tap row - Cin = 4 - has no 32-bit magic: 2^32)
+    auto quad_tap = [&](int q) { return cin4 == 1 ? q : (int)__umulhi((unsigned)q, c4magic); };
+    f32x4 vv[NU];
+    float bs[RW], gco[RW];
+    auto load_slabs = [&](int u, f32x4 *t) __attribute__((always_inline)) {          // (j, ci) order: coalesced slab rows
+        const int q = unit_q0(u) + lane;
+        const int j = quad_tap(q), c4 = q - j * cin4;
+        const unsigned off = unit_live(u) && q < n4 ? (unsigned)((j * Cb + unit_co(u)) * Ca + 4 * c4) * 4u : OUTSIDE;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            t[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_gw, (int)(s < splits ? off : OUTSIDE),
+                                                                                    (int)(slab_bytes * (unsigned)(s < splits ? s : 0)), 0));
+    };
+    auto sum_slabs = [&](int u, const f32x4 *t, int ln) __attribute__((always_inline)) {
+        const int q = unit_q0(u) + ln;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            a += s < splits ? t[s] : z;
+        }
+        if (unit_live(u) && q < n4) {
+            const int j = quad_tap(q), c4 = q - j * cin4;
+            float *dst = s_gw + (RW * w + u / (4 * P)) * (pitch * k) + j * pitch + 4 * c4;
+            dst[0] = a.x, dst[1] = a.y, dst[2] = a.z, dst[3] = a.w;
+        }
+    };
+    f32x4 t0[UB][NS];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) load_slabs(u, t0[u]);
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {                                   // natural (ci, j) order
+        const int q = unit_q0(u) + lane;
+        vv[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            r_v, (int)(unit_live(u) && q < n4 ? (unsigned)(unit_co(u) * n + 4 * q) * 4u : OUTSIDE), 0, 0));
+    }
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+        const int co = co0 + RW * w + rr;
+        gco[rr] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_g, (int)(co < Cout ? (unsigned)co * 4u : OUTSIDE), 0, 0));
+        bs[rr] = 0.f;                                                // lane sp holds bias slab sp: 0 + x, as the one-channel form
+        bs[rr] += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+            r_gb, (int)(co < Cout && lane < splits ? (unsigned)(lane * Cb + co) * 4u : OUTSIDE), 0, 0));
+    }
+    {
+        const int ln = fresh(lane);
+#pragma unroll
+        for (int u = 0; u < UB; ++u) sum_slabs(u, t0[u], ln);
+    }
+#pragma unroll
+    for (int u0 = UB; u0 < NU; u0 += UB) {
+        f32x4 t[UB][NS];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) load_slabs(u0 + u, t[u]);
+        const int ln = fresh(lane);
+#pragma unroll
+        for (int u = 0; u < UB; ++u) sum_slabs(u0 + u, t[u], ln);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rv = 0; rv < RW * 4; ++rv) {                            // one virtual wave of one channel
+        const float *s_row = s_gw + (RW * w + rv / 4) * (pitch * k);
+        float ss4 = 0.f, dot4 = 0.f;
+        if (unit_live(rv * P)) {
+            const int ln = fresh(lane);
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const int q = unit_q0(rv * P + p) + ln;
+                if (q < n4) {
+                    int at[4];
+                    quad_places(q, at);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        ss4 = __builtin_fmaf(vv[rv * P + p][e], vv[rv * P + p][e], ss4);
+                        dot4 = __builtin_fmaf(vv[rv * P + p][e], s_row[at[e]], dot4);
+                    }
+                }
+            }
+            ss4 = fin_butterfly(ss4), dot4 = fin_butterfly(dot4);
+        }
+        if (lane == 0) red[4 * RW * w + rv] = ss4, red[4 * FIN_ROWS + 4 * RW * w + rv] = dot4;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+        const int co = co0 + RW * w + rr;
+        if (co >= Cout) continue;                                    // (uniform)
+        const float *s_row = s_gw + (RW * w + rr) * (pitch * k);
+        float sst = 0.f, dott = 0.f;
+        for (int vw = 0; vw < 4; ++vw) sst += red[4 * (RW * w + rr) + vw], dott += red[4 * FIN_ROWS + 4 * (RW * w + rr) + vw];
+        const float inv = 1.f / __builtin_sqrtf(sst);
+        const float dd = dott * inv;
+        const float gs = gco[rr] * inv;
+#pragma unroll
+        for (int vp = 0; vp < 4 * P; ++vp) {
+            const int u = rr * 4 * P + vp, q = unit_q0(u) + fresh(lane);
+            if (unit_live(u) && q < n4) {
+                f32x4 o;
+                int at[4];
+                quad_places(q, at);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = gs * (s_row[at[e]] - vv[u][e] * inv * dd);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, o), r_gv,
+                                                       (int)((unsigned)(co * n + 4 * q) * 4u), 0, 0);
+            }
+        }
+        if (lane == 0) gg[co] = dd;
+        if (bias) {
+            const float b = fin_butterfly(bs[rr]);
+            if (lane == 0) gbias[co] = b;
+        }
+    }
+}
+
+// one conv of a 256-thread launch in the row-group form: block b owns the channels FIN_ROWS b ... of it
+__device__ __forceinline__ void conv_finish_rows_any(const float *gw_part, const float *gb_part, int splits, const float *v, const float *g,
+                                                     int Cout, int Cin, int k, int Cb, int Ca, float *gv, float *gg, float *gbias,
+                                                     unsigned kmagic, unsigned c4magic, const int b, float *s_gw, float *red) {
+    auto run = [&](auto ns, auto p) __attribute__((always_inline)) {
+        conv_finish_rows<decltype(ns)::value, decltype(p)::value>(gw_part, gb_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic,
+                                                                  c4magic, FIN_ROWS * b, s_gw, red);
+    };
+    auto by_slots = [&](auto p) __attribute__((always_inline)) {     // (uniform)
+        if (splits <= 2) run(std::integral_constant<int, 2>{}, p);
+        else if (splits <= 4) run(std::integral_constant<int, 4>{}, p);
+        else if (splits <= 8 || decltype(p)::value == 2) run(std::integral_constant<int, 8>{}, p);       // (two quads: splits <= 8)
+        else if constexpr (decltype(p)::value == 1) run(std::integral_constant<int, 16>{}, p);
+    };
+    if (Cin * k <= 1024) by_slots(std::integral_constant<int, 1>{});
+    else by_slots(std::integral_constant<int, 2>{});
+}
+
+template <bool MANY, int BD>   // BD threads: 1024 for MANY and for rows of 2048 and more, else 256
+__global__ __launch_bounds__(BD, FIN_WAVES(BD)) void conv_finish_kernel(const float *gw_part, const float *gb_part, int splits, const float *v,
+                                                         const float *g, int Cout, int Cin, int k, int Cb, int Ca, float *gv,
+                                                         float *gg, float *gbias, unsigned kmagic, unsigned cmagic, unsigned c4magic) {
     extern __shared__ float s_gw[];
-    __shared__ float red[32];
+    __shared__ float red[8 * FIN_ROWS];
+    if constexpr (!MANY && BD == 256) {
+        if (conv_finish_in_rows(Cin, k, Cb, Ca, splits)) {               // (uniform)
+            conv_finish_rows_any(gw_part, gb_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, c4magic, blockIdx.x, s_gw, red);
+            return;
+        }
+    }
     conv_finish_body<MANY>(gw_part, gb_part, splits, v, g, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, cmagic, blockIdx.x, s_gw, red);
 }
 
@@ -1472,17 +1695,24 @@ __global__ __launch_bounds__(1024) void conv_finish_kernel(const float *gw_part,
 // arguments (no table upload: the launch is capturable in a hipGraph as it is)
 struct FinishArgs {
     psnd_wnorm_desc d[PSND_WNORM_MAX];
-    unsigned kmagic[PSND_WNORM_MAX], cmagic[PSND_WNORM_MAX];
-    int blk0[PSND_WNORM_MAX + 1];
+    unsigned kmagic[PSND_WNORM_MAX], cmagic[PSND_WNORM_MAX], c4magic[PSND_WNORM_MAX];
+    int blk0[PSND_WNORM_MAX + 1];         // first workgroup of conv i: a conv takes ceil(Cout / FIN_ROWS) in the row-group form, else Cout
     int n;
 };
-template <bool MANY>
-__global__ __launch_bounds__(1024) void conv_finish_multi_kernel(FinishArgs a) {
+template <bool MANY, int BD>
+__global__ __launch_bounds__(BD, FIN_WAVES(BD)) void conv_finish_multi_kernel(FinishArgs a) {
     extern __shared__ float s_gw[];
-    __shared__ float red[32];
+    __shared__ float red[8 * FIN_ROWS];
     int i = 0;
     while (i + 1 < a.n && (int)blockIdx.x >= a.blk0[i + 1]) ++i;          // uniform
     const psnd_wnorm_desc &d = a.d[i];
+    if constexpr (!MANY && BD == 256) {
+        if (conv_finish_in_rows(d.Cin, d.k, d.Cb, d.Ca, d.splits)) {           // (uniform) the role of this workgroup, as the host laid blk0 out
+            conv_finish_rows_any(d.gw_part, d.gbias_part, d.splits, d.v, d.g, d.Cout, d.Cin, d.k, d.Cb, d.Ca, d.gv, d.gg, d.gbias, a.kmagic[i],
+                                 a.c4magic[i], (int)blockIdx.x - a.blk0[i], s_gw, red);
+            return;
+        }
+    }
     conv_finish_body<MANY>(d.gw_part, d.gbias_part, d.splits, d.v, d.g, d.Cin, d.k, d.Cb, d.Ca, d.gv, d.gg, d.gbias, a.kmagic[i],
                            a.cmagic[i], (int)blockIdx.x - a.blk0[i], s_gw, red);
 }
@@ -2131,17 +2361,30 @@ extern "C" int psnd_conv1d_prep_multi(const void *descs_dev, int n, int total_bl
 extern "C" int psnd_conv1d_wnorm_bwd(const float *gw_part, const float *gbias_part, int splits, const float *v, const float *g,
                                      int Cout, int Cin, int k, int Cb, int Ca, float *gv, float *gg, float *gbias, void *stream) {
     if (!gw_part || !v || !g || !gv || !gg || splits < 1) PSND_FAIL(PSND_E_ARG, "conv1d_wnorm_bwd: null pointer / splits");
-    const size_t lds = sizeof(float) * (size_t)(Cin + 1) * k;
+    size_t lds = sizeof(float) * (size_t)(Cin + 1) * k;
     if (lds > 60 * 1024) PSND_FAIL(PSND_E_SHAPE, "conv1d_wnorm_bwd: Cin*k=%d too large", Cin * k);   // + 4 KB of slab-group sums
     const unsigned kmagic = (unsigned)((0x100000000ull + (unsigned)k - 1) / (unsigned)k);
     const unsigned cmagic = (unsigned)((0x100000000ull + (unsigned)Cin - 1) / (unsigned)Cin);
+    const unsigned cin4 = Cin >= 4 ? (unsigned)Cin >> 2 : 1u, c4magic = (unsigned)((0x100000000ull + cin4 - 1) / cin4);
     const int threads = Cin * k >= 2048 ? 1024 : 256;         // big rows: 4x the loads in flight per output channel
     if (splits > 16)                                          // slab groups: 1024 threads + their partial sums (conv_finish_body)
-        hipLaunchKernelGGL(conv_finish_kernel<true>, dim3(Cout), dim3(1024), lds + 4096, static_cast<hipStream_t>(stream), gw_part,
-                           gbias_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, cmagic);
-    else
-        hipLaunchKernelGGL(conv_finish_kernel<false>, dim3(Cout), dim3(threads), lds, static_cast<hipStream_t>(stream), gw_part,
-                           gbias_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, cmagic);
+        hipLaunchKernelGGL((conv_finish_kernel<true, 1024>), dim3(Cout), dim3(1024), lds + 4096, static_cast<hipStream_t>(stream), gw_part,
+                           gbias_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, cmagic, c4magic);
+    else if (threads == 1024)
+        hipLaunchKernelGGL((conv_finish_kernel<false, 1024>), dim3(Cout), dim3(1024), lds, static_cast<hipStream_t>(stream), gw_part,
+                           gbias_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic, cmagic, c4magic);
+    else {
+        const bool rows = conv_finish_in_rows(Cin, k, Cb, Ca, splits);       // FIN_ROWS channels per workgroup (conv_finish_rows)
+        if (rows) lds *= FIN_ROWS;
+        if (lds > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_finish_kernel<false, 256>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIN_ROWS_LDS_MAX);
+            if (e != hipSuccess) PSND_FAIL(PSND_E_HIP, "conv1d_wnorm_bwd: set LDS size: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL((conv_finish_kernel<false, 256>), dim3(rows ? (Cout + FIN_ROWS - 1) / FIN_ROWS : Cout), dim3(256), lds,
+                           static_cast<hipStream_t>(stream), gw_part, gbias_part, splits, v, g, Cout, Cin, k, Cb, Ca, gv, gg, gbias, kmagic,
+                           cmagic, c4magic);
+    }
     PSND_CHECK_LAUNCH("conv1d_wnorm_bwd");
     return PSND_OK;
 }
@@ -2150,8 +2393,8 @@ extern "C" int psnd_conv1d_wnorm_bwd_multi(const psnd_wnorm_desc *descs, int n, 
     if (!descs || n < 1 || n > PSND_WNORM_MAX) PSND_FAIL(PSND_E_ARG, "conv1d_wnorm_bwd_multi: %d descriptors (1..%d)", n, PSND_WNORM_MAX);
     FinishArgs a;
     a.n = n;
-    size_t lds = 0;
-    int total = 0, maxn = 0, maxsplits = 0;
+    size_t lds = 0, lds_rows = 0;
+    int maxn = 0, maxsplits = 0;
     for (int i = 0; i < n; ++i) {
         const psnd_wnorm_desc &d = descs[i];
         if (!d.gw_part || !d.v || !d.g || !d.gv || !d.gg || d.splits < 1 || d.Cout < 1 || d.Cin < 1 || d.k < 1)
@@ -2159,20 +2402,41 @@ extern "C" int psnd_conv1d_wnorm_bwd_multi(const psnd_wnorm_desc *descs, int n, 
         const size_t l = sizeof(float) * (size_t)(d.Cin + 1) * d.k;
         if (l > 60 * 1024) PSND_FAIL(PSND_E_SHAPE, "conv1d_wnorm_bwd_multi: Cin*k=%d too large", d.Cin * d.k);
         lds = l > lds ? l : lds;
-        a.d[i] = d;
-        a.kmagic[i] = (unsigned)((0x100000000ull + (unsigned)d.k - 1) / (unsigned)d.k);
-        a.cmagic[i] = (unsigned)((0x100000000ull + (unsigned)d.Cin - 1) / (unsigned)d.Cin);
-        a.blk0[i] = total;
-        total += d.Cout;
+        const size_t lr = conv_finish_in_rows(d.Cin, d.k, d.Cb, d.Ca, d.splits) ? FIN_ROWS * l : l;
+        lds_rows = lr > lds_rows ? lr : lds_rows;
         maxn = d.Cin * d.k > maxn ? d.Cin * d.k : maxn;
         maxsplits = d.splits > maxsplits ? d.splits : maxsplits;
     }
+    const bool rows = maxsplits <= 16 && maxn < 2048;         // the 256-thread launch: its lean convs in groups of FIN_ROWS channels
+    // the kernel's table: in a 256-thread launch the one-channel convs first - their workgroups wait three times for memory and would
+    // otherwise be the launch's tail behind the row groups
+    int total = 0, m = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i) {
+            const psnd_wnorm_desc &d = descs[i];
+            const bool in_rows = rows && conv_finish_in_rows(d.Cin, d.k, d.Cb, d.Ca, d.splits);
+            if (in_rows != (pass == 1)) continue;
+            a.d[m] = d;
+            a.kmagic[m] = (unsigned)((0x100000000ull + (unsigned)d.k - 1) / (unsigned)d.k);
+            a.cmagic[m] = (unsigned)((0x100000000ull + (unsigned)d.Cin - 1) / (unsigned)d.Cin);
+            const unsigned cin4 = d.Cin >= 4 ? (unsigned)d.Cin >> 2 : 1u;
+            a.c4magic[m] = (unsigned)((0x100000000ull + cin4 - 1) / cin4);
+            a.blk0[m++] = total;
+            total += in_rows ? (d.Cout + FIN_ROWS - 1) / FIN_ROWS : d.Cout;
+        }
     a.blk0[n] = total;
-    const int threads = maxn >= 2048 ? 1024 : 256;
     if (maxsplits > 16)
-        hipLaunchKernelGGL(conv_finish_multi_kernel<true>, dim3(total), dim3(1024), lds + 4096, static_cast<hipStream_t>(stream), a);
-    else
-        hipLaunchKernelGGL(conv_finish_multi_kernel<false>, dim3(total), dim3(threads), lds, static_cast<hipStream_t>(stream), a);
+        hipLaunchKernelGGL((conv_finish_multi_kernel<true, 1024>), dim3(total), dim3(1024), lds + 4096, static_cast<hipStream_t>(stream), a);
+    else if (!rows)
+        hipLaunchKernelGGL((conv_finish_multi_kernel<false, 1024>), dim3(total), dim3(1024), lds, static_cast<hipStream_t>(stream), a);
+    else {
+        if (lds_rows > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_finish_multi_kernel<false, 256>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIN_ROWS_LDS_MAX);
+            if (e != hipSuccess) PSND_FAIL(PSND_E_HIP, "conv1d_wnorm_bwd_multi: set LDS size: %s", hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL((conv_finish_multi_kernel<false, 256>), dim3(total), dim3(256), lds_rows, static_cast<hipStream_t>(stream), a);
+    }
     PSND_CHECK_LAUNCH("conv1d_wnorm_bwd_multi");
     return PSND_OK;
 }
