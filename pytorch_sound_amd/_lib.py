@@ -189,6 +189,12 @@ class ChainPair(ctypes.Structure):
                 ('M1', _P), ('M2', _P), ('m1_slope', _F), ('m2_slope', _F)]
 
 
+class WnormDesc(ctypes.Structure):
+    """psnd_wnorm_desc of include/psnd.h"""
+    _fields_ = [('gw_part', _P), ('gbias_part', _P), ('v', _P), ('g', _P), ('gv', _P), ('gg', _P), ('gbias', _P),
+                ('splits', _INT), ('Cout', _INT), ('Cin', _INT), ('k', _INT), ('Cb', _INT), ('Ca', _INT)]
+
+
 def lib():
     """Load (once) and return the ctypes handle.  Raises if the HIP extension is absent."""
     global _lib

@@ -12,7 +12,7 @@ entirely on hand-written kernels: weight prep (weight norm + bf16 packs), implic
 gradient), split-K weight gradient with all taps / bias gradient fused, weight-norm backward.
 """
 import ctypes
-import os
+from collections import namedtuple
 from pytorch_sound_amd import _switches as _sw
 import weakref
 
@@ -471,7 +471,6 @@ def _sections(dev, N, rows):
     """PSND_CL_SECTIONS = n runs a chain as n batch sections; default 1.  Two sections took the config-2 step from 1.239 to 1.194 ms
     while the weight-gradient role was a 40 k-cycle chain per launch; with the transposing-read weight gradient (26 k cycles) one and
     two sections measure the same (1.014 / 1.017 ms), so the simpler graph is the default."""
-    import os
     e = _sw.lab('PSND_CL_SECTIONS', 'auto')
     n = 1 if e == 'auto' else int(e)
     if n <= 1 or N % n != 0 or N // n < 1 or (e == 'auto' and not AUTO_SECTIONS):
@@ -531,7 +530,6 @@ def _wgrad_streams(dev):
     round 2): 1.22 ms with 2 side streams, 1.34 with 3, 1.26 with 4 against 1.13 ms for the paired input-/weight-gradient launches
     on one stream - the branches overlap for only a fifth of their time (tools/overlap.py) and every kernel runs slower next to
     another one (wgrad 20 -> 26 us, the masked pair launch 22 us): kept as an A/B switch and for the parity tests."""
-    import os
     if _sw.lab('PSND_CL_BWD_SPLIT', '0') != '1' or not _pair_enabled() or not AUTO_SECTIONS:
         return []
     n = int(_sw.lab('PSND_CL_WGRAD_STREAMS', '3'))
@@ -542,55 +540,75 @@ def _wgrad_streams(dev):
 
 
 def _pair_enabled():
-    import os
     return _sw.lab('PSND_CL_PAIR', '1') != '0'
 
 
+# The records of ResBlockCL: built once per node, read-only.  _Step: one conv of the stack.  Forward launches: _Conv, _Pair, _Chain.
+# Backward launches: _B (input + weight gradient of one conv), _W (weight gradient alone), _Side (a _W on a side stream), _PairB (masked
+# pair launch), _ChainB, _PB (one-launch pair backward), _PBFlush; _Lag: the weight gradient a _PB carries for the pair handled before;
+# _WBatch: a conv of the one weight-gradient launch.  _Pair and _PairB name their taps as psnd_chain_pair does.
+_Step = namedtuple('_Step', 'Cout Cin k Ca Cb dil pad slope has_res has_bias role')
+_Conv = namedtuple('_Conv', 'inp wf bp res Ca Cb k off0 dil oslope raw act')
+_Pair = namedtuple('_Pair', 'inp1 wf1 bp1 slope1 mid wf2 bp2 res C k off1 dstep1 off2 dstep2 oslope raw act')
+_Chain = namedtuple('_Chain', 'inp1 res C k pairs')
+_B = namedtuple('_B', 'G1 G2 am slope wb inp Ca Cb k pad dil gx g_out ep_mask ep_slope ep_res gw gbp S')
+_W = namedtuple('_W', 'G1 G2 am slope inp Ca Cb k off0 dil gw gbp S')
+_Side = namedtuple('_Side', 'w')
+_PairB = namedtuple('_PairB', 'G wb2 m1 m1s g_h wb1 m2 m2s res C k off1 dstep1 off2 dstep2 gx flush_after')
+_ChainB = namedtuple('_ChainB', 'pairs')
+_PB = namedtuple('_PB', 'G wb2 m1 m1s g_h wb1 m2 m2s C k pad2 dil2 pad1 dil1 gx gw gbp lag')
+_PBFlush = namedtuple('_PBFlush', 'lag')
+_Lag = namedtuple('_Lag', 'g xa off0 dstep gw gbp C k')
+_WBatch = namedtuple('_WBatch', 'conv G inp off0 dstep')
+
+
+def _chain_takes(pairs):
+    """a psnd_conv1d_cl_chain launch over these pairs (_Pair or _PairB) leaves every workgroup >= 32 rows of its own"""
+    taps = [t for p in pairs for t in (p.off1, p.dstep1, p.off2, p.dstep2)]
+    return lib().psnd_conv1d_cl_chain_rows(pairs[0].C, pairs[0].k, len(pairs), (ctypes.c_int * len(taps))(*taps)) >= 32
+
+
 def _chain_pairs_bwd(plan, rows):
-    """the same for the input-gradient launches ('pairb') of the batched backward: consecutive pairs, each reading the gradient the one
+    """the same for the input-gradient launches (_PairB) of the batched backward: consecutive pairs, each reading the gradient the one
     before wrote, as one masked psnd_conv1d_cl_chain launch"""
-    import os
     mx = int(_sw.lab('PSND_CL_CHAIN_BWD', _sw.lab('PSND_CL_CHAIN', '3')))
     if mx < 2 or rows > 8192:
         return plan
     out = []
     for e in plan:
-        if e[0] == 'pairb' and e[10] == 256 and e[9] is e[1]:
-            c = out[-1] if out and out[-1][0] == 'chainb' else None
-            if c is not None and len(c[1]) < mx and c[1][-1][16] is e[1] and c[1][-1][11] == e[11]:
-                taps = [t for q_ in c[1] + [e] for t in q_[12:16]]
-                if lib().psnd_conv1d_cl_chain_rows(e[10], e[11], len(c[1]) + 1, (ctypes.c_int * len(taps))(*taps)) >= 32:
-                    c[1].append(e)
-                    continue
-            out.append(['chainb', [e]])
+        if isinstance(e, _PairB) and e.C == 256 and e.res is e.G:
+            c = out[-1] if out and isinstance(out[-1], _ChainB) else None
+            if (c is not None and len(c.pairs) < mx and c.pairs[-1].gx is e.G and c.pairs[-1].k == e.k
+                    and _chain_takes(c.pairs + [e])):
+                c.pairs.append(e)
+                continue
+            out.append(_ChainB([e]))
         else:
             out.append(e)
-    return [c[1][0] if c[0] == 'chainb' and len(c[1]) == 1 else c for c in out]
+    return [c.pairs[0] if isinstance(c, _ChainB) and len(c.pairs) == 1 else c for c in out]
 
 
 def _chain_pairs(plan, rows):
-    """Consecutive 'pair' launches of a forward plan -> 'chain' launches (psnd_conv1d_cl_chain: a workgroup carries its rows through up
+    """Consecutive _Pair launches of a forward plan -> _Chain launches (psnd_conv1d_cl_chain: a workgroup carries its rows through up
     to PSND_CL_CHAIN pairs - default 3, a ResBlock1 - on the chip; 0 switches it off).  Only where a launch is a latency chain of few
     workgroups (<= 8192 rows: the config-2 size); a pair joins the chain in front of it when it reads that chain's outputs."""
-    import os
     mx = int(_sw.lab('PSND_CL_CHAIN', '3'))
     if mx < 2 or rows > 8192:
         return plan
     out = []
     for e in plan:
-        if (e[0] == 'pair' and e[9] == 256 and e[8] is not None and e[16] is not None and e[17] is not None
-                and 0.0 <= e[4] <= 1.0 and 0.0 <= e[15] <= 1.0):
-            c = out[-1] if out and out[-1][0] == 'chain' else None
-            if c is not None and len(c[5]) < mx and c[5][-1][17] is e[1] and c[5][-1][16] is e[8] and c[3] == e[9] and c[4] == e[10]:
-                taps = [t for q_ in c[5] + [e] for t in q_[11:15]]
-                if lib().psnd_conv1d_cl_chain_rows(e[9], e[10], len(c[5]) + 1, (ctypes.c_int * len(taps))(*taps)) >= 32:
-                    c[5].append(e)
-                    continue
-            out.append(['chain', e[1], e[8], e[9], e[10], [e]])
+        if (isinstance(e, _Pair) and e.C == 256 and e.res is not None and e.raw is not None and e.act is not None
+                and 0.0 <= e.slope1 <= 1.0 and 0.0 <= e.oslope <= 1.0):
+            c = out[-1] if out and isinstance(out[-1], _Chain) else None
+            if (c is not None and len(c.pairs) < mx and c.pairs[-1].act is e.inp1 and c.pairs[-1].raw is e.res and c.C == e.C
+                    and c.k == e.k and _chain_takes(c.pairs + [e])):
+                c.pairs.append(e)
+                continue
+            out.append(_Chain(e.inp1, e.res, e.C, e.k, [e]))
         else:
             out.append(e)
     # a chain of one is the pair launch it came from
-    return [c[5][0] if c[0] == 'chain' and len(c[5]) == 1 else c for c in out]
+    return [c.pairs[0] if isinstance(c, _Chain) and len(c.pairs) == 1 else c for c in out]
 
 
 def _sec(t, h, nsec):
@@ -944,7 +962,6 @@ def prep_all(owner, convs, defer_backward_packs=False):
     written with 16-byte stores are read at full speed while fresh (the forward chains right behind the launch) but ~25 % slower 300 us
     later (input-gradient chains 38 -> 47 us each) - the per-channel kernel's 2-byte stores did not show that, at 35 us per launch."""
     import struct
-    import os
     if _sw.lab('PSND_NO_PREP_ALL') == '1':      # A/B switch: one prep launch per conv
         return None
     # psnd_conv1d_prep_multi stages 8 rows of Cin * k bf16 values in LDS: wider rows (e.g. 1024 channels x 11 taps) take the per-conv prep
@@ -1043,14 +1060,14 @@ class ResBlockCL(torch.autograd.Function):
             else:                                          # 'head' (no residual) / 'c2' / 'r2': raw + activated output
                 raw, act, res, oslope = (mk() if (not last) or want_raw else None), mk(), (cur_x if has_res else None), slope
                 cur_x, cur_xa = raw, act
-            if (role == 'c2' and _pair_enabled() and plan and plan[-1][0] == 'conv' and steps[-1][10] == 'c1' and plan[-1][5] == Ca == Cb
-                    and plan[-1][7] == k and lib().psnd_conv1d_cl_pair_supported(Ca, k, plan[-1][8], plan[-1][9], -pad, dil)):
+            c1 = plan[-1] if plan else None
+            if (role == 'c2' and _pair_enabled() and isinstance(c1, _Conv) and steps[-1].role == 'c1' and c1.Ca == Ca == Cb
+                    and c1.k == k and lib().psnd_conv1d_cl_pair_supported(Ca, k, c1.off0, c1.dil, -pad, dil)):
                 # conv1 -> conv2 of a ResBlock1 pair as ONE launch (psnd_conv1d_cl_pair): the first conv's output stays in LDS
-                _, inp1, wf1, bp1, _, _, _, _, off1, dil1, slope1, _, mid = plan.pop()
-                plan.append(('pair', inp1, wf1, bp1, slope1, mid, wf, bp, res, Ca, k, off1, dil1, -pad, dil, oslope, raw, act))
+                plan[-1] = _Pair(c1.inp, c1.wf, c1.bp, c1.oslope, c1.act, wf, bp, res, Ca, k, c1.off0, c1.dil, -pad, dil, oslope, raw, act)
             else:
-                plan.append(('conv', inp, wf, bp, res, Ca, Cb, k, -pad, dil, oslope, raw, act))
-            steps.append((Cout, Cin, k, Ca, Cb, dil, pad, slope, has_res, b is not None, role))
+                plan.append(_Conv(inp, wf, bp, res, Ca, Cb, k, -pad, dil, oslope, raw, act))
+            steps.append(_Step(Cout, Cin, k, Ca, Cb, dil, pad, slope, has_res, b is not None, role))
             saved += [inp, act if act is not None else inp, wb, v32, g32]
         nsec, sides = _sections(dev, shape.N, shape.N * shape.Lp)
         Nh = shape.N // nsec
@@ -1060,25 +1077,25 @@ class ResBlockCL(torch.autograd.Function):
             st = stream_ptr(dev)
             q = lambda t: ptr(_sec(t, h, nsec))                # noqa: E731
             for e in plan:
-                if e[0] == 'chain':
-                    _, inp1, res0, C, k, pairs = e
+                if isinstance(e, _Chain):
+                    inp1, res0, C, k, pairs = e
                     arr = (_lib.ChainPair * len(pairs))()
-                    for d, (_, _, wf1, bp1, slope1, mid, wf2, bp2, _, _, _, off1, dil1, off2, dil2, oslope, raw, act) in zip(arr, pairs):
-                        d.W1, d.bias1, d.act1_slope, d.mid_out = wf1.data_ptr(), bp1.data_ptr(), float(slope1), q(mid)
-                        d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = wf2.data_ptr(), bp2.data_ptr(), off1, dil1, off2, dil2
+                    for d, p in zip(arr, pairs):
+                        d.W1, d.bias1, d.act1_slope, d.mid_out = p.wf1.data_ptr(), p.bp1.data_ptr(), float(p.slope1), q(p.mid)
+                        d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wf2.data_ptr(), p.bp2.data_ptr(), p.off1, p.dstep1, p.off2, p.dstep2
                         # the residual stream BETWEEN the pairs of a chain never leaves the chip (nothing reads it back: the backward
                         # needs the activated tensors only); the last pair's is the next launch's
-                        d.act2_slope, d.out_raw, d.out_act = float(oslope), (q(raw) if raw is pairs[-1][16] else None), q(act)
+                        d.act2_slope, d.out_raw, d.out_act = float(p.oslope), (q(p.raw) if p is pairs[-1] else None), q(p.act)
                     check(lib().psnd_conv1d_cl_chain(q(inp1), q(res0), ctypes.addressof(arr), len(pairs), Nh, shape.Lp, shape.L, shape.HP,
                                                      C, k, st), 'psnd_conv1d_cl_chain')
                     continue
-                if e[0] == 'pair':
-                    _, inp1, wf1, bp1, slope1, mid, wf2, bp2, res, C, k, off1, dil1, off2, dil2, oslope, raw, act = e
+                if isinstance(e, _Pair):
+                    inp1, wf1, bp1, slope1, mid, wf2, bp2, res, C, k, off1, dstep1, off2, dstep2, oslope, raw, act = e
                     check(lib().psnd_conv1d_cl_pair(q(inp1), ptr(wf1), ptr(bp1), None, 1.0, float(slope1), q(mid), ptr(wf2), ptr(bp2),
-                                                    None, 1.0, q(res), Nh, shape.Lp, shape.L, shape.HP, C, k, off1, dil1, off2, dil2,
+                                                    None, 1.0, q(res), Nh, shape.Lp, shape.L, shape.HP, C, k, off1, dstep1, off2, dstep2,
                                                     float(oslope), q(raw), q(act), st), 'psnd_conv1d_cl_pair')
                     continue
-                _, inp, wf, bp, res, Ca, Cb, k, off0, dil, oslope, raw, act = e
+                inp, wf, bp, res, Ca, Cb, k, off0, dil, oslope, raw, act = e
                 check(lib().psnd_conv1d_cl(q(inp), None, None, 1.0, ptr(wf), ptr(bp), q(res), None,
                                            Nh, shape.Lp, shape.L, shape.HP, Ca, Cb, k, off0, dil, float(oslope), 1.0,
                                            q(raw), q(act), None, st), 'psnd_conv1d_cl')
@@ -1093,9 +1110,6 @@ class ResBlockCL(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_raw, g_act):
-        import os
-        import struct
-        import ctypes
         saved, steps, shape = ctx.saved_tensors, ctx.steps, ctx.shape
         dev = saved[0].device
         n = len(steps)
@@ -1137,9 +1151,7 @@ class ResBlockCL(torch.autograd.Function):
                  and shape.N * shape.Lp <= 8192)
         wbatch = []
         own_launch = []                        # (plan entry, conv): convs whose weight-gradient slabs are written by that entry itself
-        flush_after = {}                       # id(input-gradient tensor a pair launch writes) -> len(wbatch) once that launch has run
-        pair_bwd = (nsec == 1 and not wstreams and not batch and _pair_enabled() and _sw.lab('PSND_CL_PAIR_BWD', '1') != '0'
-                    and shape.N * shape.Lp <= 8192)
+        pair_bwd = nsec == 1 and not wstreams and not batch and _pair_enabled() and shape.N * shape.Lp <= 8192
         lag = None                             # weight gradient of a pair's first conv, carried to the next pair launch
         with torch.cuda.device(dev):
             # The gradient a conv receives is  g = g_raw + g_act * leaky'(own activated output).  Only the block's LAST conv gets
@@ -1149,70 +1161,60 @@ class ResBlockCL(torch.autograd.Function):
             g_comb = None                      # combined incoming gradient of conv i (None for the block's last conv)
             res_pending = None                 # pairs: gradient on the residual stream behind the pair being walked
             def slabs(i, G1, G2, am, inp, S=None):
-                Cout, Cin, k, Ca, Cb, dil, pad, slope = steps[i][:8]
+                """the weight-gradient side of conv i, in the one place: slabs, gradient destinations, weight-norm descriptor, grads;
+                returns the _W launch that fills the slabs (a _B / _PB / the batched launch takes gw, gbp, S from it instead)"""
+                s = steps[i]
                 v32, g32 = saved[5 * i + 3], saved[5 * i + 4]
                 if S is None:
-                    S = lib().psnd_conv1d_cl_wgrad_splits(Nh, shape.Lp, Ca, Cb, k)
-                gw = torch.empty((nsec * S, k, Cb, Ca), dtype=torch.float32, device=dev)    # slabs of section h: [h S, (h+1) S)
-                gbp = torch.empty((nsec * S, Cb), dtype=torch.float32, device=dev)
-                gv, gg, gb = grad_out(i, v32, g32, Cb)
-                descs[i] = struct.pack('<7Q6i', gw.data_ptr(), gbp.data_ptr(), v32.data_ptr(), g32.data_ptr(), gv.data_ptr(),
-                                       gg.data_ptr(), gb.data_ptr(), nsec * S, Cout, Cin, k, Cb, Ca)
+                    S = lib().psnd_conv1d_cl_wgrad_splits(Nh, shape.Lp, s.Ca, s.Cb, s.k)
+                gw = torch.empty((nsec * S, s.k, s.Cb, s.Ca), dtype=torch.float32, device=dev)    # slabs of section h: [h S, (h+1) S)
+                gbp = torch.empty((nsec * S, s.Cb), dtype=torch.float32, device=dev)
+                gv, gg, gb = grad_out(i, v32, g32, s.Cb)
+                descs[i] = _lib.WnormDesc(gw.data_ptr(), gbp.data_ptr(), v32.data_ptr(), g32.data_ptr(), gv.data_ptr(), gg.data_ptr(),
+                                          gb.data_ptr(), nsec * S, s.Cout, s.Cin, s.k, s.Cb, s.Ca)
                 keep.extend([gw, gbp, G1, G2])
                 grads[3 * i], grads[3 * i + 1] = gv, gg
-                grads[3 * i + 2] = gb[:Cout] if steps[i][9] else None
-                return ('w', G1, G2, am, slope, inp, Ca, Cb, k, -pad, dil, gw, gbp, S)
+                grads[3 * i + 2] = gb[:s.Cout] if s.has_bias else None
+                return _W(G1, G2, am, s.slope, inp, s.Ca, s.Cb, s.k, -s.pad, s.dil, gw, gbp, S)
 
             for i in range(n - 1, -1, -1):
                 if i == skip:
                     continue
                 Cout, Cin, k, Ca, Cb, dil, pad, slope, has_res, has_bias, role = steps[i]
-                inp, act, wb, v32, g32 = saved[5 * i:5 * i + 5]
-                if (pair_bwd and role == 'c2' and i >= 2 and steps[i - 1][10] == 'c1' and g_comb is not None and Ca == Cb
-                        and steps[i - 1][3] == steps[i - 1][4] == Ca and steps[i - 1][2] == k
-                        and lib().psnd_conv1d_cl_pair_bwd_supported(Ca, k, pad, dil, steps[i - 1][6], steps[i - 1][5])):
-                    # the whole pair's backward as ONE launch (psnd_conv1d_cl_pair_bwd): input gradients of conv2 and conv1 chained on
-                    # chip, conv2's weight gradient, and the weight gradient of the conv1 of the pair handled BEFORE (its gradient is
-                    # that launch's g_h); this pair's conv1 waits for the next such launch (or the flush after the loop)
+                inp, act, wb = saved[5 * i:5 * i + 3]
+                p = steps[i - 1] if i > 0 else None            # the conv in front of this one
+                # conv i - 1 and conv i are a residual pair (conv1, conv2) that one launch can take, given the kernel has the instance
+                pair = role == 'c2' and i >= 2 and p.role == 'c1' and g_comb is not None and Ca == Cb == p.Ca == p.Cb and p.k == k
+                one = pair and pair_bwd and lib().psnd_conv1d_cl_pair_bwd_supported(Ca, k, pad, dil, p.pad, p.dil)
+                masked = (pair and (wstreams or batch)
+                          and k == 3 and Ca in (128, 256)        # (the masked form of the pair kernel: the 3-tap instances only)
+                          and lib().psnd_conv1d_cl_pair_supported(Ca, k, pad, -dil, p.pad, -p.dil))
+                if one or masked:
                     inp1, wb1 = saved[5 * (i - 1)], saved[5 * (i - 1) + 2]
-                    d1, pad1 = steps[i - 1][5], steps[i - 1][6]
-                    G = g_comb
-                    g_h = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)
-                    gx = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)
-                    S2 = lib().psnd_conv1d_cl_pair_bwd_splits(shape.N, shape.Lp, Ca, k)
-                    wa = slabs(i, G, None, None, inp, S2)
-                    plan.append(('pb', G, wb, inp, float(steps[i - 1][7]), g_h, wb1, inp1, float(steps[i - 2][7]), Ca, k, pad, dil, pad1, d1, gx,
-                                 wa[11], wa[12], lag))
-                    wl = slabs(i - 1, g_h, None, None, inp1, S2)
-                    lag = (g_h, inp1, -pad1, d1, wl[11], wl[12], Ca, k)
-                    keep.extend([g_h, gx])
-                    res_pending = G
-                    g_comb = gx
-                    skip = i - 1
-                    continue
-                if ((wstreams or batch) and role == 'c2' and i >= 2 and steps[i - 1][10] == 'c1' and g_comb is not None and Ca == Cb
-                        and steps[i - 1][3] == steps[i - 1][4] == Ca and steps[i - 1][2] == k
-                        and k == 3 and Ca in (128, 256)          # (the masked form of the pair kernel: the 3-tap instances only)
-                        and lib().psnd_conv1d_cl_pair_supported(Ca, k, pad, -dil, steps[i - 1][6], -steps[i - 1][5])):
-                    # input gradients of conv2 and conv1 of a residual pair as ONE launch on this stream (psnd_conv1d_cl_pair with
-                    # the transposed packs, mirrored taps and the leaky' masks); their weight gradients go to the side streams, or
-                    # (batch) into the one launch behind the chain
-                    inp1, wb1 = saved[5 * (i - 1)], saved[5 * (i - 1) + 2]
-                    d1, pad1 = steps[i - 1][5], steps[i - 1][6]
-                    G = g_comb
+                    G, m1s, m2s = g_comb, float(p.slope), float(steps[i - 2].slope)
                     g_h = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)      # gradient wrt conv1's output
                     gx = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)
-                    if batch:
-                        wbatch.append((i, G, inp, -pad, dil))
+                    if one:
+                        # the whole pair's backward as ONE launch (psnd_conv1d_cl_pair_bwd): input gradients of conv2 and conv1 chained on
+                        # chip, conv2's weight gradient, and the weight gradient of the conv1 of the pair handled BEFORE (its gradient is
+                        # that launch's g_h); this pair's conv1 waits for the next such launch (or the flush after the loop)
+                        S2 = lib().psnd_conv1d_cl_pair_bwd_splits(shape.N, shape.Lp, Ca, k)
+                        wa = slabs(i, G, None, None, inp, S2)
+                        plan.append(_PB(G, wb, inp, m1s, g_h, wb1, inp1, m2s, Ca, k, pad, dil, p.pad, p.dil, gx, wa.gw, wa.gbp, lag))
+                        wl = slabs(i - 1, g_h, None, None, inp1, S2)
+                        lag = _Lag(g_h, inp1, -p.pad, p.dil, wl.gw, wl.gbp, Ca, k)
                     else:
-                        plan.append(('side',) + slabs(i, G, None, None, inp))                          # ready before the pair launch
-                    plan.append(('pairb', G, wb, inp, float(steps[i - 1][7]), g_h, wb1, inp1, float(steps[i - 2][7]), G, Ca, k,
-                                 pad, -dil, pad1, -d1, gx))
-                    if batch:
-                        wbatch.append((i - 1, g_h, inp1, -pad1, d1))
-                        flush_after[id(gx)] = len(wbatch)
-                    else:
-                        plan.append(('side',) + slabs(i - 1, g_h, None, None, inp1))
+                        # input gradients of conv2 and conv1 of a residual pair as ONE launch on this stream (psnd_conv1d_cl_pair with
+                        # the transposed packs, mirrored taps and the leaky' masks); their weight gradients go to the side streams, or
+                        # (batch) into the one launch behind the chain
+                        if batch:
+                            wbatch += [_WBatch(i, G, inp, -pad, dil), _WBatch(i - 1, g_h, inp1, -p.pad, p.dil)]
+                        else:
+                            plan.append(_Side(slabs(i, G, None, None, inp)))                           # ready before the pair launch
+                        # flush_after: len(wbatch) once this launch has run
+                        plan.append(_PairB(G, wb, inp, m1s, g_h, wb1, inp1, m2s, G, Ca, k, pad, -dil, p.pad, -p.dil, gx, len(wbatch)))
+                        if not batch:
+                            plan.append(_Side(slabs(i - 1, g_h, None, None, inp1)))
                     keep.extend([g_h, gx])
                     res_pending = G
                     g_comb = gx
@@ -1226,27 +1228,16 @@ class ResBlockCL(torch.autograd.Function):
                     need_gout = has_res and g_act is not None
                 else:
                     G1, G2, am, need_gout = g_comb, None, None, False
-                S = lib().psnd_conv1d_cl_wgrad_splits(Nh, shape.Lp, Ca, Cb, k)
-                gw = torch.empty((nsec * S, k, Cb, Ca), dtype=torch.float32, device=dev)    # slabs of section h: [h S, (h+1) S)
-                gbp = torch.empty((nsec * S, Cb), dtype=torch.float32, device=dev)
-                gv, gg, gb = None, None, None                  # (taken below, once it is known that this conv keeps its own launch)
-                g_out = torch.empty((shape.N, shape.Lp, Cb), dtype=torch.bfloat16, device=dev) if need_gout else None
-                g_here = g_out if need_gout else G1          # this conv's combined gradient (= what its residual input receives)
                 # convs outside the residual pairs (a model's head / tail) keep their own launches: with them the one weight-gradient launch
-                # grows by as much as their launches took (PSND_CL_BWD_BATCH_ENDS=1: 81 -> 122 us against 23 + 7 us saved at config 2)
-                wb_ok = batch and G2 is None and not need_gout and _sw.lab('PSND_CL_BWD_BATCH_ENDS', '0') == '1'
+                # grows by as much as their launches took (81 -> 122 us against 23 + 7 us saved at config 2)
+                w = slabs(i, G1, G2, am, inp)
+                g_out = torch.empty((shape.N, shape.Lp, Cb), dtype=torch.bfloat16, device=dev) if need_gout else None
+                keep.append(g_out)
+                g_here = g_out if need_gout else G1          # this conv's combined gradient (= what its residual input receives)
                 if i == 0 and not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
                     # the chain's input needs no gradient (features): weight gradient only
                     gx = None
-                    if wb_ok:                                  # batched backward: with all the others, in the one launch behind the chain
-                        wbatch.append((i, G1, inp, -pad, dil))
-                        keep.append(G1)
-                        if i > 0:
-                            g_comb = gx
-                        g_raw = g_act = None
-                        continue
-                    plan.append((('side',) if wstreams else ()) + ('w', G1, G2, am, slope, inp, Ca, Cb, k, -pad, dil, gw, gbp, S))
-                    g_raw = g_act = None
+                    plan.append(_Side(w) if wstreams else w)
                 else:
                     gx = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)
                     # epilogue of the input gradient: this conv's input `inp` is the previous conv's activated output
@@ -1258,42 +1249,23 @@ class ResBlockCL(torch.autograd.Function):
                         ep_mask, ep_res = inp, g_here
                     else:                                      # 'c2' -> its conv1, 'tail' -> the last conv of the stack
                         ep_mask, ep_res = inp, None
-                    if wb_ok:                                  # input gradient alone here; the weight gradient joins the batch
-                        plan.append(('b', G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask,
-                                     float(steps[i - 1][7] if i > 0 else 1.0), ep_res, None, None, S))
-                        wbatch.append((i, G1, inp, -pad, dil))
-                        keep += [G1]
-                        if role == 'c2':
-                            res_pending = g_here
-                        if i > 0:
-                            g_comb = gx
-                        elif role == 'head':
-                            g_raw, g_act = None, gx
-                        else:
-                            g_raw, g_act = (res_pending if role == 'c1' else g_here), gx
-                        continue
-                    plan.append(('b', G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask,
-                                 float(steps[i - 1][7] if i > 0 else 1.0), ep_res, gw, gbp, S))
-                gv, gg, gb = grad_out(i, v32, g32, Cb)
-                descs[i] = struct.pack('<7Q6i', gw.data_ptr(), gbp.data_ptr(), v32.data_ptr(), g32.data_ptr(), gv.data_ptr(),
-                                       gg.data_ptr(), gb.data_ptr(), nsec * S, Cout, Cin, k, Cb, Ca)
+                    plan.append(_B(G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask,
+                                   float(p.slope if i > 0 else 1.0), ep_res, w.gw, w.gbp, w.S))
                 own_launch.append((plan[-1], i))               # its slabs exist once that plan entry has run
-                keep += [gw, gbp, G1, G2, g_out]
-                grads[3 * i], grads[3 * i + 1] = gv, gg
-                grads[3 * i + 2] = gb[:Cout] if has_bias else None
+                # the hand-on to the conv in front (or, from conv 0, out of the node)
                 if role == 'c2':
                     res_pending = g_here
                 if i > 0:
                     g_comb = gx
                 elif gx is None:
-                    pass
+                    g_raw = g_act = None
                 elif role == 'head':                           # gradient wrt the chain's input buffer
                     g_raw, g_act = None, gx
                 else:                                          # gradients wrt the block's inputs (x, xa)
                     g_raw, g_act = (res_pending if role == 'c1' else g_here), gx
 
             if lag is not None:                # the chain's first pair: its conv1 weight gradient has no later pair launch to ride on
-                plan.append(('pbflush', lag))
+                plan.append(_PBFlush(lag))
             if batch:
                 plan = _chain_pairs_bwd(plan, shape.N * shape.Lp)
             used = []
@@ -1303,60 +1275,59 @@ class ResBlockCL(torch.autograd.Function):
                 q = lambda t: ptr(_sec(t, h, nsec))            # noqa: E731
                 main = torch.cuda.current_stream(dev)
                 for e in (plan if entries is None else entries):
-                    if e[0] == 'side':                         # a weight gradient on the next side stream, behind what is enqueued so far
+                    if isinstance(e, _Side):                   # a weight gradient on the next side stream, behind what is enqueued so far
                         sd = wstreams[len(used) % len(wstreams)]
                         used.append(sd)
                         ev = torch.cuda.Event()
                         ev.record(main)
                         sd.wait_event(ev)
-                        _, _, G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e
+                        G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e.w
                         with torch.cuda.stream(sd):
                             check(lib().psnd_conv1d_cl_wgrad(ptr(G1), ptr(G2), ptr(am), float(slope), ptr(inp), shape.N, shape.Lp, Ca, Cb, k,
                                                              off0, dil, ptr(gw), ptr(gbp), None, stream_ptr(dev)), 'psnd_conv1d_cl_wgrad')
                         continue
-                    if e[0] == 'pb':
-                        _, G, wb2, m1, m1s, g_h, wb1, m2, m2s, C, k, pad2, dil2, pad1, d1, gx, gwa, gba, lg = e
-                        lb = lg if lg is not None else (None, None, 0, 0, None, None, C, k)
+                    if isinstance(e, _PB):
+                        G, wb2, m1, m1s, g_h, wb1, m2, m2s, C, k, pad2, dil2, pad1, dil1, gx, gw, gbp, lg = e
+                        if lg is None:                         # the first pair walked: nothing carried yet
+                            lg = _Lag(None, None, 0, 0, None, None, C, k)
                         check(lib().psnd_conv1d_cl_pair_bwd(ptr(G), ptr(wb2), ptr(m1), m1s, ptr(g_h), ptr(wb1), ptr(m2), m2s, ptr(G), shape.N,
-                                                            shape.Lp, shape.L, shape.HP, C, k, pad2, dil2, pad1, d1, ptr(gx), ptr(m1), ptr(gwa),
-                                                            ptr(gba), ptr(lb[0]), ptr(lb[1]), lb[2], lb[3], ptr(lb[4]), ptr(lb[5]), st),
+                                                            shape.Lp, shape.L, shape.HP, C, k, pad2, dil2, pad1, dil1, ptr(gx), ptr(m1), ptr(gw),
+                                                            ptr(gbp), ptr(lg.g), ptr(lg.xa), lg.off0, lg.dstep, ptr(lg.gw), ptr(lg.gbp), st),
                               'psnd_conv1d_cl_pair_bwd')
                         continue
-                    if e[0] == 'pbflush':
-                        lg = e[1]
+                    if isinstance(e, _PBFlush):
+                        lg = e.lag
                         check(lib().psnd_conv1d_cl_pair_bwd(None, None, None, 1.0, None, None, None, 1.0, None, shape.N, shape.Lp, shape.L,
-                                                            shape.HP, lg[6], lg[7], 0, 1, 0, 1, None, None, None, None, ptr(lg[0]), ptr(lg[1]),
-                                                            lg[2], lg[3], ptr(lg[4]), ptr(lg[5]), st), 'psnd_conv1d_cl_pair_bwd')
+                                                            shape.HP, lg.C, lg.k, 0, 1, 0, 1, None, None, None, None, ptr(lg.g), ptr(lg.xa),
+                                                            lg.off0, lg.dstep, ptr(lg.gw), ptr(lg.gbp), st), 'psnd_conv1d_cl_pair_bwd')
                         continue
-                    if e[0] == 'chainb':
-                        pairs = e[1]
-                        arr = (_lib.ChainPair * len(pairs))()
-                        for d, (_, G, wb2, m1, m1s, g_h, wb1, m2, m2s, res, C, k, off1, ds1, off2, ds2, gx) in zip(arr, pairs):
-                            d.W1, d.bias1, d.act1_slope, d.mid_out = wb2.data_ptr(), None, 1.0, g_h.data_ptr()
-                            d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = wb1.data_ptr(), None, off1, ds1, off2, ds2
-                            d.act2_slope, d.out_raw, d.out_act = 1.0, gx.data_ptr(), None
-                            d.M1, d.M2, d.m1_slope, d.m2_slope = m1.data_ptr(), m2.data_ptr(), m1s, m2s
-                        G0 = pairs[0][1]
-                        check(lib().psnd_conv1d_cl_chain(ptr(G0), ptr(G0), ctypes.addressof(arr), len(pairs), shape.N, shape.Lp, shape.L,
-                                                         shape.HP, pairs[0][10], pairs[0][11], st), 'psnd_conv1d_cl_chain')
+                    if isinstance(e, _ChainB):
+                        arr = (_lib.ChainPair * len(e.pairs))()
+                        for d, p in zip(arr, e.pairs):
+                            d.W1, d.bias1, d.act1_slope, d.mid_out = p.wb2.data_ptr(), None, 1.0, p.g_h.data_ptr()
+                            d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wb1.data_ptr(), None, p.off1, p.dstep1, p.off2, p.dstep2
+                            d.act2_slope, d.out_raw, d.out_act = 1.0, p.gx.data_ptr(), None
+                            d.M1, d.M2, d.m1_slope, d.m2_slope = p.m1.data_ptr(), p.m2.data_ptr(), p.m1s, p.m2s
+                        p0 = e.pairs[0]
+                        check(lib().psnd_conv1d_cl_chain(ptr(p0.G), ptr(p0.G), ctypes.addressof(arr), len(e.pairs), shape.N, shape.Lp, shape.L,
+                                                         shape.HP, p0.C, p0.k, st), 'psnd_conv1d_cl_chain')
                         continue
-                    if e[0] == 'pairb':
-                        _, G, wb2, m1, m1s, g_h, wb1, m2, m2s, res, C, k, off1, ds1, off2, ds2, gx = e
+                    if isinstance(e, _PairB):
+                        G, wb2, m1, m1s, g_h, wb1, m2, m2s, res, C, k, off1, dstep1, off2, dstep2, gx, _ = e
                         check(lib().psnd_conv1d_cl_pair(ptr(G), ptr(wb2), None, ptr(m1), m1s, 1.0, ptr(g_h), ptr(wb1), None, ptr(m2), m2s,
-                                                        ptr(res), shape.N, shape.Lp, shape.L, shape.HP, C, k, off1, ds1, off2, ds2, 1.0,
+                                                        ptr(res), shape.N, shape.Lp, shape.L, shape.HP, C, k, off1, dstep1, off2, dstep2, 1.0,
                                                         ptr(gx), None, st), 'psnd_conv1d_cl_pair')
                         continue
-                    if e[0] == 'w':
-                        _, G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e
+                    if isinstance(e, _W):
+                        G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e
                         check(lib().psnd_conv1d_cl_wgrad(q(G1), q(G2), q(am), float(slope), q(inp), Nh, shape.Lp, Ca, Cb, k, off0, dil,
                                                          ptr(gw[h * S:(h + 1) * S]), ptr(gbp[h * S:(h + 1) * S]), None, st),
                               'psnd_conv1d_cl_wgrad')
                     else:
-                        _, G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask, ep_slope, ep_res, gw, gbp, S = e
+                        G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask, ep_slope, ep_res, gw, gbp, S = e
                         check(lib().psnd_conv1d_cl_bwd(q(G1), q(G2), q(am), float(slope), ptr(wb), q(inp), Nh, shape.Lp, shape.L,
                                                        shape.HP, Ca, Cb, k, pad, dil, q(gx), q(g_out), q(ep_mask), ep_slope, q(ep_res),
-                                                       None if gw is None else ptr(gw[h * S:(h + 1) * S]),
-                                                       None if gbp is None else ptr(gbp[h * S:(h + 1) * S]), st),
+                                                       ptr(gw[h * S:(h + 1) * S]), ptr(gbp[h * S:(h + 1) * S]), st),
                               'psnd_conv1d_cl_bwd')
 
             st = stream_ptr(dev)
@@ -1367,17 +1338,17 @@ class ResBlockCL(torch.autograd.Function):
                 for j0 in range(0, len(part), 32):
                     sub = part[j0:j0 + 32]
                     # row ranges: what suits the most frequent shape of the launch (the body's 256 -> 256 convs); the others take the same
-                    shp = [(steps[ci][3], steps[ci][4], steps[ci][2]) for ci, _, _, _, _ in sub]
-                    main_shape = max(set(shp), key=shp.count)
+                    shp = [(steps[b.conv].Ca, steps[b.conv].Cb, steps[b.conv].k) for b in sub]
+                    Ca, Cb, k = max(set(shp), key=shp.count)
                     # (a chunk of the hand-over: row ranges as if it were at least half of all the convs - the weight-norm backward
                     #  has to add every range's slab up)
-                    cnt = max(shp.count(main_shape), len(wbatch) // 2) if len(part) < len(wbatch) else shp.count(main_shape)
-                    Sb = lib().psnd_conv1d_cl_wgrad_multi_splits(shape.N, shape.Lp, main_shape[0], main_shape[1], main_shape[2], cnt)
+                    cnt = max(shp.count((Ca, Cb, k)), len(wbatch) // 2) if len(part) < len(wbatch) else shp.count((Ca, Cb, k))
+                    Sb = lib().psnd_conv1d_cl_wgrad_multi_splits(shape.N, shape.Lp, Ca, Cb, k, cnt)
                     arr = (_lib.WgradDesc * len(sub))()
-                    for d, (ci, G, inp, off0, dstep) in zip(arr, sub):
-                        w = slabs(ci, G, None, None, inp, Sb)
-                        d.g, d.xa, d.gw_part, d.gbias_part, d.off0, d.dstep = G.data_ptr(), inp.data_ptr(), w[11].data_ptr(), w[12].data_ptr(), off0, dstep
-                        d.Ca, d.Cb, d.k, d.splits = steps[ci][3], steps[ci][4], steps[ci][2], Sb
+                    for d, b in zip(arr, sub):
+                        w = slabs(b.conv, b.G, None, None, b.inp, Sb)
+                        d.g, d.xa, d.gw_part, d.gbias_part, d.off0, d.dstep = b.G.data_ptr(), b.inp.data_ptr(), w.gw.data_ptr(), w.gbp.data_ptr(), b.off0, b.dstep
+                        d.Ca, d.Cb, d.k, d.splits = w.Ca, w.Cb, w.k, Sb
                     check(lib().psnd_conv1d_cl_wgrad_multi(ctypes.addressof(arr), len(sub), shape.N, shape.Lp, st), 'psnd_conv1d_cl_wgrad_multi')
 
             def finish(convs):
@@ -1386,8 +1357,8 @@ class ResBlockCL(torch.autograd.Function):
                 ds = [descs[ci] for ci in convs]
                 for j0 in range(0, len(ds), 32):                 # PSND_WNORM_MAX descriptors per launch
                     chunk = ds[j0:j0 + 32]
-                    buf = ctypes.create_string_buffer(b''.join(chunk))
-                    check(lib().psnd_conv1d_wnorm_bwd_multi(buf, len(chunk), st), 'psnd_conv1d_wnorm_bwd_multi')
+                    arr = (_lib.WnormDesc * len(chunk))(*chunk)
+                    check(lib().psnd_conv1d_wnorm_bwd_multi(ctypes.addressof(arr), len(chunk), st), 'psnd_conv1d_wnorm_bwd_multi')
                 out = []
                 for ci in convs:
                     for ent in early.get(ci, ()):
@@ -1398,40 +1369,29 @@ class ResBlockCL(torch.autograd.Function):
                 if out:
                     sink.deliver(out)
 
-            if sink is not None and batch and nsec == 1 and not wstreams:
+            if sink is not None and batch:
                 # chunked: behind every input-gradient launch the weight gradients of the convs it completed, their weight-norm
                 # backward and their hand-over - the reducer's buckets fill (and leave) block by block, last block first
                 done_w = 0
-
-                def chunk(part, ready):
-                    if part:
-                        wgrad_batch(part)
-                    finish(ready)
-
-                launches = [e for e in plan if (e[1][-1] if e[0] == 'chainb' else e)[0] == 'pairb']
+                launches = [j for j, e in enumerate(plan) if isinstance(e, (_PairB, _ChainB))]     # positions of the pair / chain launches
                 L, C = len(launches), max(1, int(HANDOVER_CHUNKS))
-                cut = {id(launches[min(L - 1, max(0, round((j + 1) * L / C) - 1))]) for j in range(C - 1)} if L else set()
+                cut = {launches[min(L - 1, max(0, round((j + 1) * L / C) - 1))] for j in range(C - 1)} if L else set()
                 ready = []
-                for e in plan:
+                for j, e in enumerate(plan):
                     run(0, [e])
                     ready += [ci for pe, ci in own_launch if pe is e]
-                    last = e[1][-1] if e[0] == 'chainb' else e
-                    upto = flush_after.get(id(last[16])) if (last[0] == 'pairb' and id(e) in cut) else None
-                    if upto is None:
+                    if j not in cut:
                         continue                                  # no hand-over point behind this launch (own-launch convs wait for the next)
-                    part = []
-                    if upto is not None and upto > done_w:
-                        part = wbatch[done_w:upto]
-                        ready += [ci for ci, _, _, _, _ in part]
-                        done_w = upto
-                    if ready:
-                        chunk(part, ready)
-                        ready = []
+                    upto = (e.pairs[-1] if isinstance(e, _ChainB) else e).flush_after
+                    part, done_w = wbatch[done_w:upto], upto       # (upto grows from launch to launch: every pair adds its two convs)
+                    wgrad_batch(part)
+                    finish(ready + [b.conv for b in part])
+                    ready = []
                 part = wbatch[done_w:]
-                rest = [ci for ci in range(n) if ci not in handed and descs[ci] is not None and ci not in [c for c, _, _, _, _ in part]]
-                rest = [ci for ci in rest if ci not in ready]
-                if part or rest or ready:
-                    chunk(part, ready + rest + [ci for ci, _, _, _, _ in part])
+                # (the convs of `part` have no descriptor yet: wgrad_batch makes it)
+                rest = [ci for ci in range(n) if descs[ci] is not None and ci not in handed and ci not in ready]
+                wgrad_batch(part)
+                finish(ready + rest + [b.conv for b in part])
             else:
                 _run_sections(dev, nsec, sides, run)
                 for sd in set(used):
@@ -1462,7 +1422,6 @@ class _PackList(list):
 
 
 def _use_block_node(convs, x):
-    import os
     return (_sw.lab('PSND_NO_BLOCK_NODE') != '1' and x is not None and len(convs) <= 64
             and all(c.weight_v.shape[0] == c.weight_v.shape[1] for c in convs))
 
@@ -1470,7 +1429,6 @@ def _use_block_node(convs, x):
 def conv_body_cl(head, blocks, tail, x0, shape, prep=None):
     """head conv -> ResBlock1 blocks -> tail conv (the separator's whole body: conv_pre, blocks, conv_post) as ONE autograd node.
     x0: activated CL input of the head conv.  Returns the tail conv's raw output."""
-    import os
     stack = [c for b in blocks for pair in zip(b.convs1, b.convs2) for c in pair]
     if (_sw.lab('PSND_NO_BODY_NODE') == '1' or _sw.lab('PSND_NO_BLOCK_NODE') == '1' or not _stack_enabled()
             or NODE_GRANULARITY == 'block'):
@@ -1511,7 +1469,6 @@ def resblock1_stack_cl(blocks, x, xa, shape, last_act_slope=0.1, want_raw=True, 
 
 
 def _stack_enabled():
-    import os
     return _sw.lab('PSND_NO_BLOCK_STACK') != '1' and NODE_GRANULARITY != 'block'       # one node per block instead
 
 

@@ -36,6 +36,17 @@ def test_exports_every_declared_symbol(L):
     assert L.lib().psnd_version() >= 100
 
 
+def test_mirrored_structs_match_the_header(L):
+    """the ctypes mirrors of the header's descriptor structs: same field names in the same order; psnd_wnorm_desc is 7 pointers + 6 ints"""
+    txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    bodies = dict(re.findall(r'typedef struct (psnd_\w+) \{(.*?)\} \1;', txt, flags=re.S))
+    for name, mirror in (('psnd_wgrad_desc', L.WgradDesc), ('psnd_chain_pair', L.ChainPair), ('psnd_wnorm_desc', L.WnormDesc)):
+        declared = [re.search(r'(\w+)\s*$', f).group(1) for decl in bodies[name].split(';') for f in decl.split(',') if f.strip()]
+        assert [f for f, _ in mirror._fields_] == declared, name
+    assert ctypes.sizeof(L.WnormDesc) == 80
+
+
 def test_frame_contract_matches_oracle(L):
     lib = L.lib()
     for T, n, h in [(44100, 1024, 256), (8192, 1024, 256), (1323000, 4096, 1024), (700, 256, 64), (2049, 1024, 255),
