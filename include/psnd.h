@@ -661,6 +661,19 @@ int psnd_adam_step_logged(const void *table, int n_tensors, const int *chunk_ten
                           double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
                           const float *found_inf, const float *grad_scale, float *corr, float clip_value, const float *clip_coef,
                           int *flag_log, int log_slot, int log_seq, void *stream);
+/* psnd_adam_step_logged for a Trainer with an LR scheduler whose steps are still in flight (a skipped step must not advance the schedule,
+ * trainer.py:211-214, and the host learns of a skip only later): the learning rate is chosen ON THE DEVICE.  lr_ring = rows x n_groups
+ * floats in pinned, device-mapped host memory, row j = the rates of all parameter groups after j successful steps; the launch reads
+ * good = *good_count (device int) and uses lr_ring[(good % rows) * n_groups + group] in the step size and in AdamW's decay factor.  bump != 0
+ * (one launch per step: its last parameter group's): a step that is not skipped then stores good + 1.  A skipped step reads neither ring nor
+ * counter.  corr: 2 * n_tensors + 1 floats.  NULL ring or counter, rows <= 0, group outside [0, n_groups): PSND_E_ARG, nothing launched.
+ * The rate is out of reach of an argument check: where psnd_adam_step refuses lr < 0 or NaN, this launch uses whatever the ring holds - the
+ * caller checks what it writes there (Trainer does: a schedule that yields a negative or NaN rate raises before the row is written). */
+int psnd_adam_step_sched(const void *table, int n_tensors, const int *chunk_tensor, const int64_t *chunk_off, int64_t n_chunks,
+                         double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                         const float *found_inf, const float *grad_scale, float *corr, float clip_value, const float *clip_coef,
+                         int *flag_log, int log_slot, int log_seq, const float *lr_ring, int rows, int n_groups, int group,
+                         int *good_count, int bump, void *stream);
 int psnd_grad_sumsq(const void *table, int n_tensors, const int *chunk_tensor, const int64_t *chunk_off, int64_t n_chunks,
                     float clip_value, const float *grad_scale, int accumulate, float max_norm, double *partial, double *sumsq,
                     float *coef, void *stream);

@@ -23,32 +23,65 @@ constexpr int ACH = 2048;   // elements per workgroup (256 threads x 2 float4)
 
 // step += 1 and the two bias-correction factors of every tensor, in double like torch's kernels (1 - b^step cancels badly
 // in float for the first steps): corr[2 i] = 1 / (1 - b1^step), corr[2 i + 1] = 1 / sqrt(1 - b2^step)
-// flag_log (may be null): a host-visible (pinned, device-mapped) int ring {flag, seq} per slot.  The first thread leaves the step's skip flag
-// there and, behind a system-scope fence, the sequence number the host waits for - the trainer learns about a skipped (NaN) step without
-// a device-to-host copy and an event behind every optimizer launch (4 us of blit kernel + ~10 us of idle queue per config-2 step).
-__global__ __launch_bounds__(64) void adam_tick_kernel(const AdamTensor *tab, int n, double b1, double b2, const float *found_inf, float *corr,
-                                                        int *flag_log, int log_slot, int log_seq) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (flag_log && i == 0) {
-        volatile int *slot = flag_log + 2 * log_slot;
-        slot[0] = (found_inf && *found_inf != 0.f) ? 1 : 0;
-        __threadfence_system();
-        slot[1] = log_seq;
-    }
-    if (i >= n) return;
-    if (found_inf && *found_inf != 0.f) return;
+__device__ __forceinline__ void adam_tick_tensor(const AdamTensor *tab, int i, double b1, double b2, float *corr) {
     const float step = *tab[i].step + 1.f;
     *tab[i].step = step;
     corr[2 * i] = (float)(1.0 / (1.0 - pow(b1, (double)step)));
     corr[2 * i + 1] = (float)(1.0 / sqrt(1.0 - pow(b2, (double)step)));
 }
+// flag_log: a host-visible (pinned, device-mapped) int ring {flag, seq} per slot.  One thread leaves the step's skip flag there and, behind a
+// system-scope fence, the sequence number the host waits for - the trainer learns about a skipped (NaN) step without a device-to-host copy
+// and an event behind every optimizer launch (4 us of blit kernel + ~10 us of idle queue per config-2 step).
+__device__ __forceinline__ void adam_log_flag(int *flag_log, int log_slot, int log_seq, bool skip) {
+    volatile int *slot = flag_log + 2 * log_slot;
+    slot[0] = skip ? 1 : 0;
+    __threadfence_system();
+    slot[1] = log_seq;
+}
+
+// flag_log may be null
+__global__ __launch_bounds__(64) void adam_tick_kernel(const AdamTensor *tab, int n, double b1, double b2, const float *found_inf, float *corr,
+                                                        int *flag_log, int log_slot, int log_seq) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool skip = found_inf && *found_inf != 0.f;
+    if (flag_log && i == 0) adam_log_flag(flag_log, log_slot, log_seq, skip);
+    if (i >= n || skip) return;
+    adam_tick_tensor(tab, i, b1, b2, corr);
+}
+
+// adam_tick_kernel for a step whose learning rate is chosen on the device (psnd_adam_step_sched): the host cannot know, when it enqueues a
+// step, how many of the steps still in flight were skipped - so it keeps the schedule's next values in a host-visible (pinned, device-mapped)
+// ring, row j = the learning rates of all parameter groups after j successful steps, and the launch picks row *good_count.  The first
+// thread leaves the chosen value in corr[2 n] for adam_kernel and, in the launch of a step's last parameter group (bump), counts the step.
+// A skipped step reads neither the ring nor the counter.  The value is used as it stands: what the ring holds is the caller's to check.
+__global__ __launch_bounds__(64) void adam_tick_sched_kernel(const AdamTensor *tab, int n, double b1, double b2, const float *found_inf, float *corr,
+                                                              int *flag_log, int log_slot, int log_seq, const float *lr_ring, int rows, int n_groups,
+                                                              int group, int *good_count, int bump) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const bool skip = found_inf && *found_inf != 0.f;
+    if (flag_log && i == 0) adam_log_flag(flag_log, log_slot, log_seq, skip);
+    if (skip) return;
+    if (i == 0) {
+        const int good = *good_count;
+        corr[2 * n] = *(const volatile float *)(lr_ring + (long long)(good % rows) * n_groups + group);
+        if (bump) *good_count = good + 1;
+    }
+    if (i >= n) return;
+    adam_tick_tensor(tab, i, b1, b2, corr);
+}
+
+// where adam_kernel takes its learning rate from: a kernel argument (LR = float), or the value adam_tick_sched_kernel left on the device
+// (LR = const float *)
+__device__ __forceinline__ float adam_lr(float v) { return v; }
+__device__ __forceinline__ float adam_lr(const float *p) { return *p; }
 
 // chunk_tensor[b], chunk_off[b]: tensor index and first element of workgroup b's chunk
-template <bool DECOUPLED>
-__global__ __launch_bounds__(256) void adam_kernel(const AdamTensor *tab, const int *chunk_tensor, const long long *chunk_off, float lr,
+template <bool DECOUPLED, typename LR = float>
+__global__ __launch_bounds__(256) void adam_kernel(const AdamTensor *tab, const int *chunk_tensor, const long long *chunk_off, LR lr_in,
                                                    float b1, float b2, float omb1, float omb2, float eps, float wd, const float *found_inf,
                                                    const float *grad_scale, const float *corr, float clip_value, const float *clip_coef) {
     if (found_inf && *found_inf != 0.f) return;
+    const float lr = adam_lr(lr_in);
     const int ti = chunk_tensor[blockIdx.x];
     const AdamTensor T = tab[ti];
     const long long e0 = chunk_off[blockIdx.x];
@@ -203,6 +236,39 @@ extern "C" int psnd_adam_step_logged(const void *table, int n_tensors, const int
         hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, s, tab, chunk_tensor, reinterpret_cast<const long long *>(chunk_off),
                            (float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, found_inf, grad_scale, corr, clip_value, clip_coef);
     PSND_CHECK_LAUNCH("adam_step");
+    return PSND_OK;
+}
+
+// psnd_adam_step_logged with the learning rate read on the device: row (*good_count % rows) of lr_ring (rows x n_groups floats in pinned,
+// device-mapped host memory), column `group`.  corr holds 2 * n_tensors + 1 floats here (the last one carries the chosen rate from the tick
+// launch to the update launch).  bump != 0 (the launch of a step's last parameter group): a step that is not skipped counts itself.
+extern "C" int psnd_adam_step_sched(const void *table, int n_tensors, const int *chunk_tensor, const int64_t *chunk_off, int64_t n_chunks,
+                                    double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                                    const float *found_inf, const float *grad_scale, float *corr, float clip_value, const float *clip_coef,
+                                    int *flag_log, int log_slot, int log_seq, const float *lr_ring, int rows, int n_groups, int group,
+                                    int *good_count, int bump, void *stream) {
+    if (flag_log && log_slot < 0) PSND_FAIL(PSND_E_ARG, "adam_step_sched: log_slot=%d", log_slot);
+    if (!table || !chunk_tensor || !chunk_off || !corr) PSND_FAIL(PSND_E_ARG, "adam_step_sched: null pointer");
+    if (!lr_ring || !good_count) PSND_FAIL(PSND_E_ARG, "adam_step_sched: null lr_ring or good_count");
+    if (rows <= 0 || n_groups <= 0 || group < 0 || group >= n_groups)
+        PSND_FAIL(PSND_E_ARG, "adam_step_sched: rows=%d n_groups=%d group=%d", rows, n_groups, group);
+    if (!(clip_value >= 0.f)) PSND_FAIL(PSND_E_ARG, "adam_step_sched: clip_value=%g", (double)clip_value);
+    if (n_tensors < 0 || n_chunks < 0 || n_chunks > 0x7fffffff) PSND_FAIL(PSND_E_SHAPE, "adam_step_sched: n_tensors=%d n_chunks=%lld", n_tensors, (long long)n_chunks);
+    if (!(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || !(weight_decay >= 0.))
+        PSND_FAIL(PSND_E_ARG, "adam_step_sched: betas=(%g, %g) eps=%g weight_decay=%g", beta1, beta2, eps, weight_decay);
+    if (n_tensors == 0 || n_chunks == 0) return PSND_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const AdamTensor *tab = static_cast<const AdamTensor *>(table);
+    hipLaunchKernelGGL(adam_tick_sched_kernel, dim3((n_tensors + 63) / 64), dim3(64), 0, s, tab, n_tensors, beta1, beta2, found_inf, corr, flag_log, log_slot, log_seq,
+                       lr_ring, rows, n_groups, group, good_count, bump ? 1 : 0);
+    const float *lr_dev = corr + 2 * (size_t)n_tensors;
+    if (decoupled)
+        hipLaunchKernelGGL((adam_kernel<true, const float *>), dim3((unsigned)n_chunks), dim3(256), 0, s, tab, chunk_tensor, reinterpret_cast<const long long *>(chunk_off),
+                           lr_dev, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, found_inf, grad_scale, corr, clip_value, clip_coef);
+    else
+        hipLaunchKernelGGL((adam_kernel<false, const float *>), dim3((unsigned)n_chunks), dim3(256), 0, s, tab, chunk_tensor, reinterpret_cast<const long long *>(chunk_off),
+                           lr_dev, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, found_inf, grad_scale, corr, clip_value, clip_coef);
+    PSND_CHECK_LAUNCH("adam_step_sched");
     return PSND_OK;
 }
 

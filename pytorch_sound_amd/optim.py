@@ -22,6 +22,10 @@ class Adam(torch.optim.Optimizer):
     # `optimizer.flag_log = (pinned int32 ring tensor (R, 2), slot, seq)` for one step(): the launch leaves found_inf and the sequence number
     # in host-visible memory (psnd_adam_step_logged) - the trainer's NaN log needs no device-to-host copy
     _supports_flag_log = True
+    # `optimizer.lr_ahead = (pinned fp32 ring tensor (rows, n_groups), rows, device int32 counter)` for one step(): the learning rate of every
+    # group is read ON THE DEVICE from ring row (counter % rows) and the launch of the last group counts a step that was not skipped
+    # (psnd_adam_step_sched) - `group['lr']` is not read.  The trainer's LR schedulers on the device-skip path (lr_ahead.py).
+    _supports_lr_ahead = True
     _decoupled = False                          # True: AdamW (weight decay applied to the parameter, not the gradient)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
@@ -72,7 +76,7 @@ class Adam(torch.optim.Optimizer):
         return {'device': device, 'static': static, 'gptrs': None, 'table': None, 'grads': None,
                 'chunk_tensor': torch.from_numpy(np.concatenate(which)).to(device),
                 'chunk_off': torch.from_numpy(np.concatenate(off)).to(device),
-                'corr': torch.empty(2 * len(params), dtype=torch.float32, device=device)}
+                'corr': torch.empty(2 * len(params) + 1, dtype=torch.float32, device=device)}     # (+ 1: the rate psnd_adam_step_sched picked)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -132,7 +136,7 @@ class Adam(torch.optim.Optimizer):
                 stable = all(g is p.grad for g, p in zip(grads, params))
                 plan['gptrs'] = gptrs if stable else None
                 plan['grads'] = None if stable else grads
-            work.append((group, plan, len(params)))
+            work.append((group, plan, len(params), gi))
         coef = None
         if max_norm > 0.0 and work:
             device = work[0][1]['device']
@@ -144,7 +148,7 @@ class Adam(torch.optim.Optimizer):
                                                  'coef': torch.ones(2, dtype=torch.float32, device=device)}
             gs = grad_scale.to(device=device, dtype=torch.float32) if grad_scale is not None else None
             with torch.cuda.device(device):
-                for wi, (group, plan, n) in enumerate(work):
+                for wi, (group, plan, n, _) in enumerate(work):
                     if plan.get('partial') is None:
                         plan['partial'] = torch.empty(plan['chunk_off'].numel(), dtype=torch.float64, device=device)
                     check(lib().psnd_grad_sumsq(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
@@ -155,12 +159,32 @@ class Adam(torch.optim.Optimizer):
             self.last_grad_norm = coef[1]
         flag_log = getattr(self, 'flag_log', None)
         self.flag_logged = flag_log is not None and len(work) > 0           # (no launch, no record: the caller falls back to a copy)
-        for wi, (group, plan, n) in enumerate(work):
+        lr_ahead = getattr(self, 'lr_ahead', None)
+        self.lr_ahead_used = lr_ahead is not None and len(work) > 0         # (no launch: no step was counted on the device)
+        if lr_ahead is not None:
+            lr_ring, lr_rows, good_count = lr_ahead
+            n_groups = len(self.param_groups)
+            if (lr_ring.dtype != torch.float32 or lr_ring.is_cuda or not lr_ring.is_pinned() or not lr_ring.is_contiguous()
+                    or lr_ring.numel() < int(lr_rows) * n_groups):
+                raise _lib.PsndError('lr_ahead: the ring must be a pinned, contiguous fp32 host tensor of rows x %d values' % n_groups)
+            if good_count.dtype != torch.int32 or not good_count.is_cuda or good_count.numel() != 1:
+                raise _lib.PsndError('lr_ahead: the counter must be one int32 on the HIP device')
+        for wi, (group, plan, n, gi) in enumerate(work):
             device = plan['device']
             b1, b2 = group['betas']
             log_ptr, log_slot, log_seq = (ptr(flag_log[0]), int(flag_log[1]), int(flag_log[2])) if (flag_log is not None and wi == 0) else (None, 0, 0)
             fi = found_inf.to(device=device, dtype=torch.float32) if found_inf is not None else None
             gs = grad_scale.to(device=device, dtype=torch.float32) if grad_scale is not None else None
+            if lr_ahead is not None:
+                if good_count.device != device:
+                    raise _lib.PsndError('lr_ahead: counter on %s, parameters on %s' % (good_count.device, device))
+                with torch.cuda.device(device):
+                    check(lib().psnd_adam_step_sched(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
+                                                     plan['chunk_off'].numel(), float(b1), float(b2), float(group['eps']),
+                                                     float(group['weight_decay']), int(self._decoupled), ptr(fi), ptr(gs), ptr(plan['corr']),
+                                                     clip_value, ptr(coef), log_ptr, log_slot, log_seq, ptr(lr_ring), int(lr_rows), n_groups, gi,
+                                                     ptr(good_count), int(wi == len(work) - 1), stream_ptr(device)), 'psnd_adam_step_sched')
+                continue
             with torch.cuda.device(device):
                 check(lib().psnd_adam_step_logged(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
                                                   plan['chunk_off'].numel(), float(group['lr']), float(b1), float(b2), float(group['eps']),

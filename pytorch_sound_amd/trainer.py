@@ -235,8 +235,15 @@ class Trainer:
             return
         self._opt_adopted = False
         opt = self.optimizer
-        if not self.adopt_optimizer or type(opt) not in (torch.optim.Adam, torch.optim.AdamW) or 'step' in opt.__dict__:
-            return                                    # (an LR scheduler patched the instance's step(): leave it alone)
+        if not self.adopt_optimizer or type(opt) not in (torch.optim.Adam, torch.optim.AdamW):
+            return
+        # an LR scheduler's constructor patches the INSTANCE's step() with a wrapper that notes `_opt_called` (torch's "scheduler before
+        # optimizer" warning).  The wrapper binds the class's step it saw, so it is taken off and an equivalent one put back after the class
+        # swap; any other instance-level patch is left alone
+        sched_wrapper = opt.__dict__.get('step')
+        if sched_wrapper is not None and not (getattr(sched_wrapper, '_wrapped_by_lr_sched', False)
+                                              and getattr(sched_wrapper, '__wrapped__', None) is type(opt).step):
+            return
         from torch.optim import optimizer as topt
         if (getattr(opt, '_optimizer_step_pre_hooks', None) or getattr(opt, '_optimizer_step_post_hooks', None)
                 or getattr(topt, '_global_optimizer_pre_hooks', None) or getattr(topt, '_global_optimizer_post_hooks', None)):
@@ -252,8 +259,22 @@ class Trainer:
             decoupled.add(g.get('decoupled_weight_decay', type(opt) is torch.optim.AdamW))
         if not decoupled <= {True, False} or len(decoupled) != 1:
             return                                    # groups that disagree, or a value the kernel does not implement
+        if sched_wrapper is not None:
+            del opt.__dict__['step']
         opt.__class__ = poptim.AdamW if decoupled == {True} else poptim.Adam
         opt._plans = {}
+        if sched_wrapper is not None:
+            import functools
+            import weakref
+            opt_ref, func = weakref.ref(opt), type(opt).step
+
+            @functools.wraps(func)
+            def wrapper(*args, **kwargs):
+                o = opt_ref()
+                o._opt_called = True
+                return func.__get__(o, o.__class__)(*args, **kwargs)
+            wrapper._wrapped_by_lr_sched = True
+            opt.step = wrapper
         self._opt_adopted = True
         self._log('optimizer %s adopted: its steps run as one HIP launch (pytorch_sound_amd.optim)' % type(opt).__name__)
 
@@ -276,7 +297,7 @@ class Trainer:
     def _watch_host_state(self) -> bool:
         """graph_steps = 'auto' and a step could still be captured: an eager forward() is watched for host-side decisions"""
         return (self.graph_steps == 'auto' and self._graph_auto_ok is not False and getattr(self, '_reducer', None) is None
-                and self.async_nan_check and self.scheduler is None and getattr(self.optimizer, '_step_supports_amp_scaling', False)
+                and self.async_nan_check and self._scheduler_rides_along() and getattr(self.optimizer, '_step_supports_amp_scaling', False)
                 and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing())
 
     def _forward_resolved(self, *inputs, is_logging: bool = False, watch: bool = False):
@@ -474,6 +495,7 @@ class Trainer:
                     self.save(i)
         except KeyboardInterrupt:
             self._log('Train is canceled !!')
+        self.sync_scheduler()                          # the scheduler the caller looks at next has taken every step of the run
         return self.best_valid_loss
 
     def clip_grad(self):
@@ -489,15 +511,127 @@ class Trainer:
     # ---- NaN skip without a host sync --------------------------------------------------------------
     # The reference tests `loss != loss` on the host every step (trainer.py:205): a device->host sync that
     # idles the GPU between forward and backward.  When the optimizer implements the AMP `found_inf`
-    # protocol (fused Adam/AdamW/SGD) and no scheduler is attached, the same decision is taken ON THE DEVICE:
+    # protocol (fused Adam/AdamW/SGD) and no scheduler is attached (or one that rides along, `async_scheduler` below), the same decision is taken ON THE DEVICE:
     # the flag isnan(loss) (MAX-all-reduced under DDP, asynchronously) is handed to the optimizer kernel, which
     # skips the update (and its step count) itself; the log line is emitted as soon as the flag has reached the
     # host on its own.  Anything else falls back to the reference's synchronous check.
     async_nan_check = True
 
     def _can_skip_on_device(self, loss: torch.Tensor) -> bool:
-        return (self.async_nan_check and loss.is_cuda and self.scheduler is None
+        return (self.async_nan_check and loss.is_cuda and self._scheduler_rides_along()
                 and getattr(self.optimizer, '_step_supports_amp_scaling', False))
+
+    # ---- LR schedulers on the device-skip path ---------------------------------------------------------------
+    # The reference steps its scheduler after every SUCCESSFUL step (trainer.py:211-214): a skipped step does not advance the schedule, and
+    # on this path the host learns of a skip only a few steps later (the flag ring above).  So the learning rate of a step in flight is chosen
+    # ON THE DEVICE: a shadow of the scheduler (lr_ahead.py) runs ahead of the real one and fills a pinned ring, row j = the rates of all
+    # groups after j successful steps; the optimizer launch reads row (good_count % rows) and counts the step itself when it is not skipped
+    # (psnd_adam_step_sched).  The REAL scheduler.step() is replayed in order as the flags are confirmed - once per step that succeeded,
+    # never for a skipped one - so `scheduler.last_epoch`, `get_last_lr()` and `param_groups[i]['lr']` follow the reference's trajectory
+    # exactly, a few steps late; `sync_scheduler()` (and logging steps, validate, save, load, the end of run()) brings them up to date.
+    # Rows that can still be read are those of the confirmed count .. confirmed count + steps in flight: fewer than _LR_RING - 2 of them.
+    # A learning rate written by hand, or a scheduler stepped by the caller, differs from what the Trainer last left there: the Trainer
+    # then catches up, rebuilds the shadow from the present state and resets the counter - the edit holds from the next step on, as on the
+    # synchronous path.  CALL sync_scheduler() BEFORE SUCH AN EDIT: without it the rates being edited are a few steps late and the scheduler
+    # steps of the steps in flight are replayed ON TOP of the edit - the same thing for a factor (`lr *= 0.1`) on a chainable scheduler, but an
+    # absolute value (`lr = 1e-4`) is then decayed further by StepLR / ExponentialLR, and overwritten by a closed-form one, than the
+    # synchronous loop would have.
+    # False, a scheduler that is not eligible (ReduceLROnPlateau, momentum cycling, foreign objects), CPU tensors or an optimizer without
+    # the `lr_ahead` protocol: the reference's synchronous check, as before.
+    async_scheduler = True
+    _LR_RING = 256
+    _lr_state = None
+
+    def _scheduler_rides_along(self) -> bool:
+        """no scheduler, or one whose steps can be chosen on the device"""
+        if self.scheduler is None:
+            return True
+        if not (self.async_scheduler and getattr(self.optimizer, '_supports_lr_ahead', False)
+                and getattr(self.optimizer, '_supports_flag_log', False)):
+            return False
+        known = getattr(self, '_lr_eligible', None)
+        if known is None or known[0] is not self.scheduler:
+            from pytorch_sound_amd import lr_ahead
+            why = lr_ahead.why_not_eligible(self.scheduler)
+            if why is None and getattr(self.scheduler, 'optimizer', None) is not self.optimizer:
+                why = 'it schedules another optimizer'
+            if why is not None:
+                self._log('scheduler %s: %s - its steps wait for the host (the synchronous NaN check)' % (type(self.scheduler).__name__, why))
+            known = self._lr_eligible = (self.scheduler, why is None)
+        return known[1]
+
+    def _lr_fingerprint(self):
+        sch = self.scheduler
+        return ([g['lr'] for g in self.optimizer.param_groups], getattr(sch, 'last_epoch', None), getattr(sch, '_step_count', None))
+
+    def _lr_rebuild(self, device):
+        """shadow, ring and counter from the scheduler's present state (nothing of this Trainer is in flight)"""
+        from pytorch_sound_amd import lr_ahead
+        st = self._lr_state
+        ahead = lr_ahead.LookAhead(self.scheduler, keep=self._LR_RING)
+        if st is None or st['ring'].shape != (self._LR_RING, ahead.n_groups) or st['count'].device != device:
+            st = self._lr_state = {'ring': torch.zeros((self._LR_RING, ahead.n_groups), dtype=torch.float32).pin_memory(),
+                                   'count': torch.zeros((), dtype=torch.int32, device=device)}
+            st['ring_np'] = st['ring'].numpy()
+        else:
+            st['count'].zero_()
+        st.update(ahead=ahead, good=0, filled=-1, seen=self._lr_fingerprint(), stale=False)
+        return st
+
+    def _lr_stage(self, device):
+        """before the optimizer launch: every row the launch may read is in the ring; returns optimizer.lr_ahead"""
+        st = self._lr_state
+        rows = self._LR_RING
+        if st is not None and len(self._nan_pending) >= rows - 2:
+            self._poll_nan_log(block=True)             # the shadow is a whole ring ahead of the confirmed steps: let the host catch up
+        # edited by hand / stepped by the caller (seen here, or by a poll that replayed scheduler steps on top of the edit: `stale`):
+        # catch up, then start from what is there now
+        if st is not None and (st['stale'] or st['seen'] != self._lr_fingerprint() or st['ring'].shape[0] != rows):
+            st = None
+        if st is None:
+            self._poll_nan_log(block=True)
+            st = self._lr_rebuild(device)
+        top = st['good'] + len(self._nan_pending)      # this step's count of successes before it: st['good'] .. top
+        try:
+            fresh = [(j, st['ahead'].row(j)) for j in range(st['filled'] + 1, top + 1)]
+        except ValueError:
+            # a schedule that ends (OneCycleLR's total_steps: "Tried to step N times"): `top` counts the steps in flight as successes, skipped
+            # ones included, and may lie past an end the run itself never reaches.  The shadow has half-taken that step: catch up and begin
+            # a new one from the real scheduler - row 0, the rates the groups hold now, needs no step of the shadow.  Any other error is the
+            # caller's (an lr_lambda that raises) and goes up as it is.
+            from pytorch_sound_amd import lr_ahead
+            if not any(hasattr(s, 'total_steps') for s in lr_ahead.members(self.scheduler)):
+                raise
+            self._poll_nan_log(block=True)
+            st = self._lr_rebuild(device)
+            fresh = [(0, st['ahead'].row(0))]
+        for j, row in fresh:
+            if not all(v >= 0.0 for v in row):         # (NaN fails too) what psnd_adam_step refuses as an argument must not reach the ring
+                raise ValueError('the scheduler yields the learning rates %r after %d more successful steps: '
+                                 'the optimizer takes finite rates >= 0' % (row, j))
+            st['ring_np'][j % rows] = row              # (fp32 image of the double, rounded as the kernel argument of psnd_adam_step is)
+            st['filled'] = j
+        return (st['ring'], rows, st['count'])
+
+    def _lr_confirmed(self, skipped: bool):
+        """a step's flag has reached the host (in order): the real scheduler takes the step the device already took"""
+        st = self._lr_state
+        if skipped or st is None:
+            return
+        if st['seen'] != self._lr_fingerprint():
+            # a rate written by hand (or a scheduler stepped by the caller) since the Trainer last looked: the step is replayed on top of
+            # it, as the synchronous loop would have, but `seen` keeps the difference - _lr_stage rebuilds the shadow before the next launch
+            st['stale'] = True
+        self.scheduler.step()
+        st['good'] += 1
+        if not st['stale']:
+            st['seen'] = self._lr_fingerprint()
+
+    def sync_scheduler(self):
+        """wait for the steps in flight and replay their scheduler steps: `scheduler` and `param_groups[i]['lr']` are then exactly where
+        the reference's loop would have them (call it before reading or editing a learning rate between steps)"""
+        if self._lr_state is not None:
+            self._poll_nan_log(block=True)
 
     # The skip flag reaches the host without a device-to-host copy when the optimizer can leave it in host-visible memory itself
     # (pytorch_sound_amd.optim: psnd_adam_step_logged writes {flag, seq} into a pinned ring): a blit kernel + an event behind every
@@ -518,13 +652,20 @@ class Trainer:
         if block and torch.cuda.is_available():
             torch.cuda.synchronize()
         keep = []
+        in_order = self._lr_state is not None          # scheduler steps are replayed in the order of the training steps
         for entry in pending:
             step, host_flag, event = entry
+            if in_order and keep:
+                keep.append(entry)
+                continue
             if isinstance(event, int):                 # ring slot: host_flag = the slot, event = the sequence number to wait for
                 ring = self._nan_ring_buf
                 if int(ring[host_flag, 1]) == event:
-                    if int(ring[host_flag, 0]) != 0:
+                    skipped = int(ring[host_flag, 0]) != 0
+                    if skipped:
                         self._log('{} cur step NAN is occured'.format(step))
+                    if in_order:
+                        self._lr_confirmed(skipped)
                 else:
                     keep.append(entry)
                 continue
@@ -585,7 +726,7 @@ class Trainer:
     # eager, so nothing of RCCL is ever captured.  The replayed backward writes its gradients into static tensors of
     # the graph's memory pool; under DDP they are copied into the flat buckets of FlatGradReducer (one multi-tensor
     # copy, the per-bucket backward hooks are deferred to one all-reduce after the replay).  Requirements:
-    # CUDA inputs, no scheduler, an optimizer with the found_inf protocol (fused Adam/AdamW/SGD), a forward()
+    # CUDA inputs, no scheduler or one whose rate is chosen on the device (async_scheduler), an optimizer with the found_inf protocol (fused Adam/AdamW/SGD), a forward()
     # free of host synchronisation.  Logging steps and the first `graph_warmup` steps of a signature run eagerly.
     #
     # graph_steps = 'auto' (default, round 6): capture when it is SAFE to - no gradient reducer (a data-parallel run opts in with True, all
@@ -612,7 +753,7 @@ class Trainer:
     static_prepare = False
 
     def _train_graph(self, step: int, batch) -> bool:
-        if not (self.async_nan_check and self.scheduler is None
+        if not (self.async_nan_check and self._scheduler_rides_along()
                 and getattr(self.optimizer, '_step_supports_amp_scaling', False)
                 and all(isinstance(t, torch.Tensor) and t.is_cuda for t in batch)):
             return False
@@ -804,9 +945,14 @@ class Trainer:
             self._nan_seq += 1
             slot, seq = self._nan_seq % self._NAN_RING, self._nan_seq
             self.optimizer.flag_log = (ring, slot, seq)
+        sched = self.scheduler is not None             # (_can_skip_on_device / _train_graph let it here: its steps are chosen on the device)
         self.optimizer.found_inf = flag
         self.optimizer.grad_scale = grad_scale
         try:
+            if sched:
+                if not use_ring:
+                    raise RuntimeError('a scheduler on the device-skip path needs the optimizer on the loss\'s HIP device')
+                self.optimizer.lr_ahead = self._lr_stage(flag.device)      # (may raise what the user's schedule raises)
             self.optimizer.step()
         finally:
             del self.optimizer.found_inf
@@ -815,6 +961,17 @@ class Trainer:
                 del self.optimizer.fused_clip
             if use_ring:
                 del self.optimizer.flag_log
+            if sched and hasattr(self.optimizer, 'lr_ahead'):
+                del self.optimizer.lr_ahead
+        if sched and not getattr(self.optimizer, 'lr_ahead_used', False):
+            # no parameter had a gradient: nothing was launched, nothing counted on the device - this one step is settled on the host
+            self._poll_nan_log(block=True)
+            if float(flag.item()) > 0:
+                self._log('{} cur step NAN is occured'.format(step))
+            else:
+                self.scheduler.step()
+            self._lr_state = None                      # (rebuilt from the scheduler's state at the next step)
+            return
         if use_ring and getattr(self.optimizer, 'flag_logged', False):
             self._nan_pending.append((step, slot, seq))    # written by the optimizer launch itself
         else:
@@ -851,6 +1008,8 @@ class Trainer:
         use_graph = self.graph_steps is True or (self.graph_steps == 'auto' and self._graph_auto_ok is not False and self._reducer is None)
         if use_graph and not log_flag and self._train_graph(step, batch):
             return
+        if log_flag:
+            self.sync_scheduler()                      # a learning rate that forward() logs is the exact one
         if self._reducer is not None:
             self._reducer.zero_grad()
         else:
@@ -867,6 +1026,7 @@ class Trainer:
                     pass
             return
 
+        self.sync_scheduler()                          # (steps of the device-skip path still in flight take their scheduler steps first)
         if self._loss_is_nan(loss):
             self._log('{} cur step NAN is occured'.format(step))
             return
@@ -930,6 +1090,7 @@ class Trainer:
         return self.save_prefix + '/' + self._bare_model.__class__.__name__
 
     def load(self, load_optim: bool = True):
+        self.sync_scheduler()                          # (the states loaded below differ from what the look-ahead last saw: it is rebuilt)
         save_path = os.path.join(self.model_dir, self.save_name)
         check_files = glob.glob(os.path.join(save_path, '*'))
         if not check_files:
@@ -944,10 +1105,12 @@ class Trainer:
             self.optimizer.load_state_dict(state_dict['optim'])
         if self.scheduler is not None:
             self.scheduler.load_state_dict(state_dict['scheduler'])
+            self._lr_state = None
         self.step = state_dict['step']
         self._log('checkpoint \'{}\' is loaded. previous step={}'.format(latest_file, self.step))
 
     def save(self, step: int):
+        self.sync_scheduler()
         if not pdist.is_main():
             self.cur_best_valid_loss = self.best_valid_loss
             return

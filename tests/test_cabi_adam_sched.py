@@ -1,0 +1,64 @@
+"""psnd_adam_step_sched (no GPU): exported, declared in include/psnd.h, mirrored by the ctypes table, and every bad argument is turned
+down with the error code before anything is launched."""
+import ctypes
+import os
+import re
+
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.fixture(scope='module')
+def L():
+    from pytorch_sound_amd import _build, _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _build.build(verbose=False)
+    return _lib
+
+
+def test_symbol_is_exported_and_declared(L):
+    txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    m = re.search(r'int\s+psnd_adam_step_sched\s*\((.*?)\)\s*;', txt, flags=re.S)
+    assert m, 'include/psnd.h does not declare psnd_adam_step_sched'
+    args = [a.strip() for a in m.group(1).split(',')]
+    names = [re.search(r'(\w+)$', a).group(1) for a in args]
+    assert names[-8:] == ['log_seq', 'lr_ring', 'rows', 'n_groups', 'group', 'good_count', 'bump', 'stream']
+    for want in ('lr_ring', 'rows', 'n_groups', 'group', 'good_count', 'bump', 'flag_log', 'found_inf', 'grad_scale', 'clip_coef'):
+        assert want in names, want
+    assert hasattr(ctypes.CDLL(L.LIB_PATH), 'psnd_adam_step_sched')
+    res, argtypes = L.SIGNATURES['psnd_adam_step_sched']
+    assert res is ctypes.c_int and len(argtypes) == len(args)
+    for a, t in zip(args, argtypes):                                      # pointers, ints, doubles and the one float line up with the header
+        kind = (ctypes.c_void_p if '*' in a else ctypes.c_double if a.startswith('double') else ctypes.c_float if a.startswith('float')
+                else ctypes.c_int64 if a.startswith('int64_t') else ctypes.c_int)
+        assert t is kind, (a, t)
+    assert L.lib().psnd_version() >= 142
+    # the existing entry points keep their signatures
+    assert len(L.SIGNATURES['psnd_adam_step'][1]) == 17 and len(L.SIGNATURES['psnd_adam_step_logged'][1]) == 20
+
+
+def test_bad_arguments_are_refused_without_a_launch(L):
+    lib = L.lib()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+
+    def call(table=p, n=1, n_chunks=1, b1=0.9, b2=0.999, eps=1e-8, wd=0.0, corr=p, clip=0.0, flag_log=None, slot=0, ring=p, rows=4,
+             n_groups=2, group=0, count=p, bump=1):
+        return lib.psnd_adam_step_sched(table, n, p, p, n_chunks, b1, b2, eps, wd, 0, None, None, corr, clip, None, flag_log, slot, 7,
+                                        ring, rows, n_groups, group, count, bump, None)
+
+    assert call(ring=None) == -1 and b'lr_ring' in lib.psnd_last_error()
+    assert call(count=None) == -1
+    assert call(rows=0) == -1 and call(rows=-3) == -1
+    assert call(group=2) == -1 and call(group=5) == -1 and call(group=-1) == -1 and b'group' in lib.psnd_last_error()
+    assert call(n_groups=0) == -1
+    assert call(table=None) == -1 and call(corr=None) == -1
+    assert call(b1=1.0) == -1 and call(b2=-0.1) == -1 and call(eps=-1.0) == -1 and call(wd=-1.0) == -1
+    assert call(clip=-1.0) == -1
+    assert call(flag_log=p, slot=-1) == -1
+    assert call(n=-1) == -2 and call(n_chunks=1 << 31) == -2
+    # nothing to do is fine - and is checked AFTER the arguments (a bad ring is refused even for an empty group)
+    assert call(n=0, n_chunks=0) == 0
+    assert call(n=0, n_chunks=0, ring=None) == -1
