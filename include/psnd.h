@@ -158,6 +158,42 @@ size_t psnd_istft_mr_scratch_bytes(int64_t N, int64_t F, int n_fft);
 int psnd_istft_mr(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop, const void *plan, size_t plan_bytes,
                   float eps, void *scratch, size_t scratch_bytes, float *out, void *stream);
 
+/* ---- masked inverse STFT on (re, im): separator to waveform, both directions ----------------------------------------------------
+ *  Forward: psnd_istft's definition applied to the spectrum S = m (re + i im) - per frame window * irDFT(S_f), the imaginary parts of
+ *  the DC and Nyquist bins dropped, overlap-add, divided by env[t] + eps (env[t] = sum_f window^2[t - f hop]), n_fft / 2 trimmed on
+ *  both sides; out (N, (F - 1) hop) fp32, fully overwritten.  eps = 0 is torch.istft's convention, 1e-9 STFT.inverse's.
+ *    re, im : (N, K, F) fp32;  mask : (N, K, F) fp32 or NULL;  m by mask_kind: PSND_MASK_NONE 1 (mask must be NULL), PSND_MASK_LINEAR
+ *    the mask, PSND_MASK_SIGMOID 1 / (1 + e^{-mask}) evaluated in the kernel (mask must not be NULL for the two).  mask * |X| e^{i arg X}
+ *    is mask * X: no magnitude, no phase, no sin / cos between the mixture and the output.
+ *  psnd_istft_reim: the power-of-two plans - a loader mode of psnd_istft's three kernel families, same dispatch, grid limits and errors.
+ *      The output is zeroed by a kernel launch of its own (not a memset node), so a hipGraph capture replays it as it ran.
+ *  psnd_istft_reim_mr: the mixed-radix plans - psnd_istft_mr's contract (plan_bytes, scratch of psnd_istft_mr_scratch_bytes, two
+ *      launches, no float atomic).
+ *  psnd_istft_reim_bwd: gradients for g = d loss / d out, (N, (F - 1) hop), either plan kind (told apart by n_fft; plan_bytes must be that
+ *      plan's size), three launches on the caller's stream, no allocation, no synchronisation:
+ *        1. gp[t] = g[t - p] / (env[t] + eps) for p <= t < L - p (p = n_fft / 2, L = (F - 1) hop + n_fft), 0 outside and where the
+ *           denominator is 0; env from the plan's window, at most ceil(n_fft / hop) taps, frames ascending, no atomics
+ *        2. A = psnd_stft_fwd / psnd_stft_mr_fwd of gp with PSND_FRAMING_NONE -> scratch
+ *        3. are = s_k Re A, aim = s_k Im A (s_k = 1 / n_fft at DC and Nyquist, 2 / n_fft elsewhere; aim = 0 at DC and Nyquist);
+ *           g_re = m are, g_im = m aim, g_m = re are + im aim; g_mask = g_m (LINEAR) or g_m sigma (1 - sigma) (SIGMOID, sigma
+ *           recomputed from the logits)
+ *      g_re and g_im: both or neither; g_mask: only with a mask; at least one output.  hop <= n_fft.
+ *      psnd_istft_reim_bwd_scratch_bytes(N, F, n_fft) = 4 (r4(N F n_fft) + 2 r4(N K F)) with r4 = rounded up to a multiple of 4
+ *      (0 for N <= 0, F <= 1 or an uncovered n_fft).
+ *  PSND_E_ARG: a NULL required pointer, a mask pointer that does not agree with mask_kind, a bad mask_kind, plan_bytes of another
+ *  plan, a scratch that is NULL or too small; PSND_E_UNSUPPORTED: an uncovered n_fft; N = 0 or F <= 1: PSND_OK, nothing launched. */
+#define PSND_MASK_NONE 0
+#define PSND_MASK_LINEAR 1
+#define PSND_MASK_SIGMOID 2
+int psnd_istft_reim(const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft, int hop,
+                    const void *plan, float eps, float *out, void *stream);
+int psnd_istft_reim_mr(const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft, int hop,
+                       const void *plan, size_t plan_bytes, float eps, void *scratch, size_t scratch_bytes, float *out, void *stream);
+size_t psnd_istft_reim_bwd_scratch_bytes(int64_t N, int64_t F, int n_fft);
+int psnd_istft_reim_bwd(const float *g, const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F,
+                        int n_fft, int hop, const void *plan, size_t plan_bytes, float eps, void *scratch, size_t scratch_bytes,
+                        float *g_re, float *g_im, float *g_mask, void *stream);
+
 /* ---- mel projection + log + clamp: replaces transforms.py:235-243, :364-365,
  *      interface/hifi_gan.py:58-61 -------------------------------------------------------- */
 #define PSND_LOG_NONE 0  /* linear mel                                   */

@@ -12,6 +12,7 @@ FRAMING_CENTER = 0
 FRAMING_HIFIGAN = 1
 FRAMING_NONE = 2
 LOG_NONE, LOG_E, LOG_10 = 0, 1, 2
+MASK_NONE, MASK_LINEAR, MASK_SIGMOID = 0, 1, 2
 
 _c = ctypes
 _P = _c.c_void_p
@@ -46,6 +47,10 @@ SIGNATURES = {
     'psnd_stft_mr_bwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _c.c_size_t, _F, _P, _P, _P, _P, _c.c_size_t, _P, _P]),
     'psnd_istft_mr_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT]),
     'psnd_istft_mr': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P]),
+    'psnd_istft_reim': (_INT, [_P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _F, _P, _P]),
+    'psnd_istft_reim_mr': (_INT, [_P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P]),
+    'psnd_istft_reim_bwd_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT]),
+    'psnd_istft_reim_bwd': (_INT, [_P, _P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P, _P, _P]),
     'psnd_mel_plan_bytes': (_c.c_size_t, [_INT, _INT]),
     'psnd_mel_plan_build': (_INT, [_INT, _INT, _P, _P]),
     'psnd_mel_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P]),

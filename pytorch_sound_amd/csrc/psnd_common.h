@@ -208,6 +208,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_uniform_rsrc(const void *
     return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
+// effective mask of psnd_istft_reim* from the stored value: 1, the value, or its logistic function (e^{+big} = inf gives an exact 0)
+__device__ __forceinline__ float reim_mask(int kind, float v) {
+    if (kind == PSND_MASK_SIGMOID) return 1.f / (1.f + __expf(-v));
+    return kind == PSND_MASK_LINEAR ? v : 1.f;
+}
+
+// the window inside a device copy of the mixed-radix plan (psnd_stft_mr.hip)
+const float *psnd_stft_mr_plan_window(const void *plan);
+
 // log epilogue of the mel kernels: log(max(mel, pre) + off), pre < 0 disables the inner max
 __device__ __forceinline__ float log_apply(float mel, int kind, float off, float pre) {
     float v = mel;

@@ -31,6 +31,9 @@ struct StftBwdParams {
     // inverse-STFT mode (psnd_istft): gmag = magnitude, gre = phase, gwav = output (N, T = (F-1)*hop)
     int win_off;        // float offset of the raw window inside the plan
     float inv_n, env_eps;
+    // the same on the complex spectrum (psnd_istft_reim): gmag = re, gre = im, mask (N, K, F) or NULL, mask_kind = PSND_MASK_*
+    const float *mask;
+    int mask_kind;
     // multi_stft_loss mode (psnd_stft_bwd_msl): gmag = TARGET magnitudes; the gradient of the loss w.r.t. the magnitude is formed
     // from the recomputed |X| inside the kernel (loss_bwd_kernel of psnd_loss.hip): norms = (||t - p||, ||t||) per clip, g = upstream
     const float *msl_norms, *msl_g;
@@ -55,18 +58,22 @@ struct StftBwdParams {
 // were a serial latency chain (~55 us per tile at one wave per SIMD).
 struct GVal {
     float a, b;      // FROM_MAG: a = gmag ; FROM_REIM: a = gre (+ gmag in c), b = gim ; ISTFT: a = magnitude, b = phase
-    float c;
+    float c;         // ISTFT on (re, im): a = re, b = im, c = mask value
 };
-template <bool FROM_MAG, bool FROM_REIM, bool ISTFT>
+template <bool FROM_MAG, bool FROM_REIM, bool ISTFT, bool REIM = false>
 struct GLoad {
     const float *gmag, *gre, *gim;
     float eps, inv_n;
     bool valid;
+    const float *mask;      // REIM only
+    int mask_kind;
     __device__ __forceinline__ GVal fetch(int off) const {
         GVal v{0.f, 0.f, 0.f};
         if (!valid) return v;
         if constexpr (ISTFT) {
             v.a = gmag[off], v.b = gre[off];
+            if constexpr (REIM)
+                if (mask) v.c = mask[off];
         } else {
             if constexpr (FROM_MAG) v.c = gmag[off];
             if constexpr (FROM_REIM) v.a = gre[off], v.b = gim[off];
@@ -79,6 +86,12 @@ struct GLoad {
     __device__ __forceinline__ void operator()(const GVal &v, float xr, float xi, float &gr, float &gi, bool edge = false) const {
         gr = 0.f, gi = 0.f;
         if (!valid) return;
+        if constexpr (ISTFT && REIM) {      // the spectrum is m (re + i im)
+            const float m = reim_mask(mask_kind, v.c) * (edge ? inv_n : 2.f * inv_n);
+            gr = m * v.a;
+            gi = m * v.b;
+            return;
+        }
         if constexpr (ISTFT) {
             float sn, cs;
             sincosf(v.b, &sn, &cs);
@@ -120,8 +133,9 @@ __device__ __forceinline__ long long reflect64(long long i, long long T) {
     return i;
 }
 
-template <int R1, int L, bool FROM_MAG, bool FROM_REIM, bool ISTFT = false>
+template <int R1, int L, bool FROM_MAG, bool FROM_REIM, bool ISTFT = false, bool REIM = false>
 __global__ __launch_bounds__(256) void stft_bwd_kernel(StftBwdParams p) {
+    static_assert(!REIM || ISTFT, "(re, im) is a loader mode of the inverse transform");
     using G = Cfg<R1, L>;
     constexpr int C = G::C, NFFT = G::NFFT, FT = G::FT, P1R = G::P1R, LB = G::LB, RB = G::RB, SF = G::SF, ROW = G::ROW;
 
@@ -164,9 +178,10 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(StftBwdParams p) {
             float uAr[L], uAi[L], uBr[L], uBi[L];  // adjoint inputs Zs[q + R1 p] in natural p order
             const long long F = p.F;
             const size_t cbase = (size_t)clip * (size_t)(C + 1) * (size_t)F + (size_t)(f0 + f2);
-            GLoad<FROM_MAG, FROM_REIM, ISTFT> gload{(FROM_MAG || ISTFT) ? p.gmag + cbase : nullptr,
-                                                    (FROM_REIM || ISTFT) ? p.gre + cbase : nullptr,
-                                                    FROM_REIM ? p.gim + cbase : nullptr, p.mag_eps, p.inv_n, (f0 + f2) < F};
+            GLoad<FROM_MAG, FROM_REIM, ISTFT, REIM> gload{(FROM_MAG || ISTFT) ? p.gmag + cbase : nullptr,
+                                                          (FROM_REIM || ISTFT) ? p.gre + cbase : nullptr,
+                                                          FROM_REIM ? p.gim + cbase : nullptr, p.mag_eps, p.inv_n, (f0 + f2) < F,
+                                                          (REIM && p.mask) ? p.mask + cbase : nullptr, REIM ? p.mask_kind : 0};
             const int iF = (int)F;
             const int stepF = R1 * iF;
             const int offA = qA * iF, offB = qB * iF;
@@ -411,9 +426,10 @@ __device__ __forceinline__ void fast_sincos(float x, float &sn, float &cs) {
     cs = __builtin_amdgcn_cosf(f);
 }
 
-template <bool ISTFT, int R1 = 32, int L_ = 16, bool MSL = false>
+template <bool ISTFT, int R1 = 32, int L_ = 16, bool MSL = false, bool REIM = false>
 __global__ __launch_bounds__((L_ == 32 ? 512 : 256), (L_ == 32 ? 1 : 2)) void stft_bwd_n1024_mag_kernel(StftBwdParams p) {
     static_assert(!(ISTFT && MSL), "the fused loss gradient is a mode of the STFT adjoint");
+    static_assert(!REIM || ISTFT, "(re, im) is a loader mode of the inverse transform");
     using G = BwdGeom<R1, L_>;
     constexpr int L = G::L, NT = G::NT, C = G::C, NFFT = G::NFFT, FT = G::FT, FPR = G::FPR, NR = G::NR, TPB = G::TPB, ROW = G::ROW, VKP = G::VKP;
     constexpr int RB = ct::ilog2(R1), LB = ct::ilog2(L), SF = G::SF;
@@ -504,6 +520,31 @@ __global__ __launch_bounds__((L_ == 32 ? 512 : 256), (L_ == 32 ? 1 : 2)) void st
         });
         if (special && fvalid2) pNy = pbase[L * stepF];
     }
+    // (re, im) loader: g* hold re, p* hold im; the mask values of the same bins are loaded together, then folded into both
+    if constexpr (REIM) {
+        if (p.mask_kind != PSND_MASK_NONE) {
+            const float *mbase = p.mask + goff;
+            float mAl[L / 2], mAh[L / 2], mBl[L / 2], mBh[L / 2], mNy = 0.f;
+            static_for<0, L / 2>([&](auto pc) __attribute__((always_inline)) {
+                constexpr int pp = decltype(pc)::value;
+                mAl[pp] = fvalid2 ? mbase[offA + pp * stepF] : 0.f;
+                mBh[pp] = fvalid2 ? mbase[offB + (L - 1 - pp) * stepF] : 0.f;
+                mBl[pp] = fvalid2 ? mbase[offB + pp * stepF] : 0.f;
+                mAh[pp] = fvalid2 ? mbase[offA + (L - 1 - pp) * stepF] : 0.f;
+            });
+            if (special && fvalid2) mNy = mbase[L * stepF];
+            const int kind = p.mask_kind;
+            static_for<0, L / 2>([&](auto pc) __attribute__((always_inline)) {
+                constexpr int pp = decltype(pc)::value;
+                const float a = reim_mask(kind, mAl[pp]), b = reim_mask(kind, mBh[pp]);
+                const float c = reim_mask(kind, mBl[pp]), d = reim_mask(kind, mAh[pp]);
+                gAl[pp] *= a, pAl[pp] *= a, gBh[pp] *= b, pBh[pp] *= b;
+                gBl[pp] *= c, pBl[pp] *= c, gAh[pp] *= d, pAh[pp] *= d;
+            });
+            const float e = reim_mask(kind, mNy);
+            gNy *= e, pNy *= e;
+        }
+    }
     __syncthreads();
     PSND_BSTAMP(1);
 
@@ -584,11 +625,17 @@ __global__ __launch_bounds__((L_ == 32 ? 512 : 256), (L_ == 32 ? 1 : 2)) void st
         };
         // inverse transform: spectrum values instead of gradients.  H[k] = m_k e^{i phi_k} * 2/n, conj(H[C-k]) likewise
         auto pair_inv = [&](v2f &a, v2f &b, v2f v, float mk, float phk, float mc, float phc) __attribute__((always_inline)) {
-            float sk, ck, sc, cc;
-            fast_sincos(phk, sk, ck);
-            fast_sincos(phc, sc, cc);
-            const float ak = mk * 2.f * p.inv_n, ac = mc * 2.f * p.inv_n;
-            const v2f ha = v2f{ak * ck, ak * sk}, hbc = v2f{ac * cc, -ac * sc};
+            v2f ha, hbc;
+            if constexpr (REIM) {                                    // (mk, phk) = masked (re, im) of bin k, (mc, phc) of bin C - k
+                const float s2 = 2.f * p.inv_n;
+                ha = v2f{s2 * mk, s2 * phk}, hbc = v2f{s2 * mc, -s2 * phc};
+            } else {
+                float sk, ck, sc, cc;
+                fast_sincos(phk, sk, ck);
+                fast_sincos(phc, sc, cc);
+                const float ak = mk * 2.f * p.inv_n, ac = mc * 2.f * p.inv_n;
+                ha = v2f{ak * ck, ak * sk}, hbc = v2f{ac * cc, -ac * sc};
+            }
             const v2f s = ha + hbc, d = ha - hbc;
             const v2f e = pk::cmul_conj(d, v);
             a = s + e;
@@ -615,7 +662,10 @@ __global__ __launch_bounds__((L_ == 32 ? 512 : 256), (L_ == 32 ? 1 : 2)) void st
             // (element p lives in slot bitrev(p)).
             // gradient (or spectrum value) of a bin; `ph` and `edge` only matter for the inverse transform
             auto gof = [&](float gm, float xr, float xi, float &gr, float &gi, float ph = 0.f, bool edge = false) __attribute__((always_inline)) {
-                if constexpr (ISTFT) {
+                if constexpr (REIM) {                                // gm = masked re, ph = masked im
+                    const float sc = edge ? p.inv_n : 2.f * p.inv_n;
+                    gr = sc * gm, gi = sc * ph;
+                } else if constexpr (ISTFT) {
                     float sn, cs;
                     fast_sincos(ph, sn, cs);
                     const float m = gm * (edge ? p.inv_n : 2.f * p.inv_n);
@@ -1065,7 +1115,7 @@ __device__ __forceinline__ void lds_fft_radix2(float *sr, float *si, int C, int 
     }
 }
 
-template <bool FROM_MAG, bool FROM_REIM, bool ISTFT = false>
+template <bool FROM_MAG, bool FROM_REIM, bool ISTFT = false, bool REIM = false>
 __global__ __launch_bounds__(256) void stft_bwd_generic_kernel(StftBwdParams p, int n_fft) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int C = n_fft / 2;
@@ -1104,7 +1154,10 @@ __global__ __launch_bounds__(256) void stft_bwd_generic_kernel(StftBwdParams p, 
             gr = g * xkr, gi = g * xki;
         }
         if (FROM_REIM) gr += p.gre[off], gi += p.gim[off];
-        if (ISTFT) {
+        if (ISTFT && REIM) {
+            const float m = reim_mask(p.mask_kind, p.mask ? p.mask[off] : 1.f) * ((k == 0 || k == C) ? p.inv_n : 2.f * p.inv_n);
+            gr = m * p.gmag[off], gi = m * p.gre[off];
+        } else if (ISTFT) {
             float sn, cs;
             sincosf(p.gre[off], &sn, &cs);
             const float m = p.gmag[off] * ((k == 0 || k == C) ? p.inv_n : 2.f * p.inv_n);
@@ -1163,13 +1216,13 @@ int launch_bwd(const StftBwdParams &p, bool from_mag, bool from_reim, hipStream_
     return PSND_OK;
 }
 
-template <int R1, int L>
+template <int R1, int L, bool REIM>
 int launch_istft(const StftBwdParams &p, hipStream_t stream) {
     constexpr size_t lds = sizeof(float) * Cfg<R1, L>::LDS_FLOATS;
     int grid = p.total_tiles;
     if (grid > 2048) grid = 2048;
     grid = (grid + 7) & ~7;
-    auto kern = stft_bwd_kernel<R1, L, false, false, true>;
+    auto kern = stft_bwd_kernel<R1, L, false, false, true, REIM>;
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) PSND_FAIL(PSND_E_HIP, "istft: set LDS size: %s", hipGetErrorString(e));
@@ -1194,11 +1247,11 @@ static bool span_bwd_ok(int n_fft, int hop) {
     return false;
 }
 
-template <bool ISTFT, int R1, int L, bool MSL>
+template <bool ISTFT, int R1, int L, bool MSL, bool REIM = false>
 static int launch_span_bwd_one(const StftBwdParams &p, hipStream_t s) {
     using G = BwdGeom<R1, L>;
     constexpr size_t lds = sizeof(float) * G::LDS_FLOATS;
-    auto kern = stft_bwd_n1024_mag_kernel<ISTFT, R1, L, MSL>;
+    auto kern = stft_bwd_n1024_mag_kernel<ISTFT, R1, L, MSL, REIM>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) PSND_FAIL(PSND_E_HIP, "stft_bwd(span): set LDS size: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(kern, dim3((p.total_tiles + 7) & ~7), dim3(G::NT), lds, s, p);
@@ -1206,11 +1259,11 @@ static int launch_span_bwd_one(const StftBwdParams &p, hipStream_t s) {
     return PSND_OK;
 }
 
-template <bool ISTFT, bool MSL>
+template <bool ISTFT, bool MSL, bool REIM = false>
 static int launch_span_bwd(int n_fft, const StftBwdParams &p, hipStream_t s) {
     switch (n_fft) {
-        case 512: return launch_span_bwd_one<ISTFT, 16, 16, MSL>(p, s);
-        case 1024: return launch_span_bwd_one<ISTFT, 32, 16, MSL>(p, s);
+        case 512: return launch_span_bwd_one<ISTFT, 16, 16, MSL, REIM>(p, s);
+        case 1024: return launch_span_bwd_one<ISTFT, 32, 16, MSL, REIM>(p, s);
         case 2048:
             if constexpr (!ISTFT) return launch_span_bwd_one<false, 32, 32, MSL>(p, s);
     }
@@ -1333,45 +1386,253 @@ extern "C" int psnd_stft_bwd_msl(const float *wav, int64_t N, int64_t T, int n_f
 // STFT.inverse (pytorch_sound/models/transforms.py:71-101): conv_transpose1d with pinv(n/h * basis)^T * window
 // == (h/n) * window * irDFT per frame, overlap-added, divided by the squared-window envelope (+eps), scaled
 // by n/h and trimmed by n/2 on both sides: out[t] = OLA(w * irfft(X_f))[t + n/2] / (env[t + n/2] + eps).
-extern "C" int psnd_istft(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop,
-                          const void *plan, float eps, float *out, void *stream) {
-    if (!mag || !phase || !plan || !out) PSND_FAIL(PSND_E_ARG, "istft: null pointer");
-    if (hop <= 0 || N < 0 || F < 0) PSND_FAIL(PSND_E_ARG, "istft: hop=%d N=%lld F=%lld", hop, (long long)N, (long long)F);
-    if (psnd_stft_plan_bytes(n_fft) == 0) PSND_FAIL(PSND_E_UNSUPPORTED, "istft: n_fft=%d unsupported", n_fft);
+// zeros for the samples the tiles add to atomically, as a launch of its own (psnd_istft_reim).  Not hipMemsetAsync: captured into a hipGraph
+// by torch.cuda.graph, the memset node stopped zeroing some of these samples on replays that followed further allocations of the process
+// (measured with psnd_istft and with this entry point: stale values of 1.0 and 2e32 in the head samples of a clip); a kernel node replays
+// as it was captured.
+static __global__ __launch_bounds__(256) void istft_zero_kernel(float *x, long long total) {
+    const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 + 4 <= total && (reinterpret_cast<uintptr_t>(x + i0) & 15) == 0) {
+        *reinterpret_cast<f32x4 *>(x + i0) = f32x4{0.f, 0.f, 0.f, 0.f};
+        return;
+    }
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < total) x[i0 + j] = 0.f;
+}
+
+// REIM: (a, b) = (re, im) with an optional mask instead of (magnitude, phase) - psnd_istft_reim, `what` names the entry point
+template <bool REIM>
+static int istft_impl(const char *what, const float *a, const float *b, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft,
+                      int hop, const void *plan, float eps, float *out, void *stream) {
+    if (!a || !b || !plan || !out) PSND_FAIL(PSND_E_ARG, "%s: null pointer", what);
+    if (REIM && (mask_kind < PSND_MASK_NONE || mask_kind > PSND_MASK_SIGMOID || (mask != nullptr) != (mask_kind != PSND_MASK_NONE)))
+        PSND_FAIL(PSND_E_ARG, "%s: mask_kind=%d with a %s mask", what, mask_kind, mask ? "non-NULL" : "NULL");
+    if (hop <= 0 || N < 0 || F < 0) PSND_FAIL(PSND_E_ARG, "%s: hop=%d N=%lld F=%lld", what, hop, (long long)N, (long long)F);
+    if (psnd_stft_plan_bytes(n_fft) == 0) PSND_FAIL(PSND_E_UNSUPPORTED, "%s: n_fft=%d unsupported", what, n_fft);
     const int64_t T = (F - 1) * hop;
     if (N == 0 || F <= 1) return PSND_OK;
     const int64_t K = n_fft / 2 + 1;
-    if (K * F >= (int64_t)1 << 31 || T >= ((int64_t)1 << 31) - 4 * (int64_t)n_fft) PSND_FAIL(PSND_E_SHAPE, "istft: clip too long");
+    if (K * F >= (int64_t)1 << 31 || T >= ((int64_t)1 << 31) - 4 * (int64_t)n_fft) PSND_FAIL(PSND_E_SHAPE, "%s: clip too long", what);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t me = hipMemsetAsync(out, 0, sizeof(float) * (size_t)N * (size_t)T, s);
-    if (me != hipSuccess) PSND_FAIL(PSND_E_HIP, "istft: memset: %s", hipGetErrorString(me));
+    if (REIM) {
+        const size_t quads = ((size_t)N * (size_t)T + 3) / 4;
+        if ((quads + 255) / 256 > 0x7fffffff) PSND_FAIL(PSND_E_SHAPE, "%s: grid too large", what);
+        hipLaunchKernelGGL(istft_zero_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, out, (long long)((size_t)N * (size_t)T));
+        PSND_CHECK_LAUNCH("istft_reim(zero)");
+    } else {
+        hipError_t me = hipMemsetAsync(out, 0, sizeof(float) * (size_t)N * (size_t)T, s);
+        if (me != hipSuccess) PSND_FAIL(PSND_E_HIP, "%s: memset: %s", what, hipGetErrorString(me));
+    }
     StftBwdParams p;
-    p.wav = nullptr, p.plan = static_cast<const float *>(plan), p.gmag = mag, p.gre = phase, p.gim = nullptr, p.gwav = out;
+    p.wav = nullptr, p.plan = static_cast<const float *>(plan), p.gmag = a, p.gre = b, p.gim = nullptr, p.gwav = out;
     p.T = T, p.F = F, p.hop = hop, p.pad = n_fft / 2, p.mag_eps = 0.f;
     p.inv_n = 1.0f / (float)n_fft, p.env_eps = eps;
+    p.mask = mask, p.mask_kind = mask_kind;
     const Decomp *d = find_decomp(n_fft);
     if (d) {
         const PlanLayout lay = plan_layout(n_fft, d->R1, d->L);
         p.win_off = lay.win;
         const int FT = 512 / d->R1;
         const int64_t ntile = (F + FT - 1) / FT;
-        if (ntile * N >= (int64_t)1 << 31) PSND_FAIL(PSND_E_SHAPE, "istft: too many tiles");
+        if (ntile * N >= (int64_t)1 << 31) PSND_FAIL(PSND_E_SHAPE, "%s: too many tiles", what);
         p.ntile = (int)ntile, p.total_tiles = (int)(ntile * N);
         switch (n_fft) {
-            case 256: return launch_istft<16, 8>(p, s);
+            case 256: return launch_istft<16, 8, REIM>(p, s);
             case 512:
-                if (span_bwd_ok(512, hop)) return launch_span_bwd<true, false>(512, p, s);
-                return launch_istft<16, 16>(p, s);
+                if (span_bwd_ok(512, hop)) return launch_span_bwd<true, false, REIM>(512, p, s);
+                return launch_istft<16, 16, REIM>(p, s);
             case 1024:
-                if (span_bwd_ok(1024, hop)) return launch_span_bwd<true, false>(1024, p, s);
-                return launch_istft<32, 16>(p, s);
-            case 2048: return launch_istft<32, 32>(p, s);
+                if (span_bwd_ok(1024, hop)) return launch_span_bwd<true, false, REIM>(1024, p, s);
+                return launch_istft<32, 16, REIM>(p, s);
+            case 2048: return launch_istft<32, 32, REIM>(p, s);
         }
     }
-    if (F > 0x7fffffff || N > 65535) PSND_FAIL(PSND_E_SHAPE, "istft(generic): grid too large");
+    if (F > 0x7fffffff || N > 65535) PSND_FAIL(PSND_E_SHAPE, "%s(generic): grid too large", what);
     p.win_off = 0, p.ntile = 0, p.total_tiles = 0;
     const size_t lds = sizeof(float) * (size_t)(2 * n_fft + 2);
-    hipLaunchKernelGGL((stft_bwd_generic_kernel<false, false, true>), dim3((unsigned)F, (unsigned)N), dim3(256), lds, s, p, n_fft);
-    PSND_CHECK_LAUNCH("istft(generic)");
+    hipLaunchKernelGGL((stft_bwd_generic_kernel<false, false, true, REIM>), dim3((unsigned)F, (unsigned)N), dim3(256), lds, s, p, n_fft);
+    PSND_CHECK_LAUNCH(REIM ? "istft_reim(generic)" : "istft(generic)");
+    return PSND_OK;
+}
+
+extern "C" int psnd_istft(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop,
+                          const void *plan, float eps, float *out, void *stream) {
+    return istft_impl<false>("istft", mag, phase, nullptr, PSND_MASK_NONE, N, F, n_fft, hop, plan, eps, out, stream);
+}
+
+// The inverse transform of the spectrum m (re + i im): the same kernels with the (re, im) loader (no magnitude, no phase, no sin / cos)
+extern "C" int psnd_istft_reim(const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft, int hop,
+                               const void *plan, float eps, float *out, void *stream) {
+    return istft_impl<true>("istft_reim", re, im, mask, mask_kind, N, F, n_fft, hop, plan, eps, out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// backward of psnd_istft_reim / psnd_istft_reim_mr: prepare -> forward transform (no padding) -> combine.  The two kernels here are
+// HBM-bound streams over four consecutive floats per thread: one 16-byte access where every tensor of the launch starts on a 16-byte
+// boundary (a row is only 4-byte aligned: the quads run over the flat tensor, not over rows), four 4-byte accesses otherwise.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ f32x4 load_quad(const float *x, long long i0, long long total, bool vec) {
+    if (vec && i0 + 4 <= total) return *reinterpret_cast<const f32x4 *>(x + i0);
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < total) v[j] = x[i0 + j];
+    return v;
+}
+
+__device__ __forceinline__ void store_quad(float *x, long long i0, long long total, bool vec, f32x4 v) {
+    if (vec && i0 + 4 <= total) {
+        *reinterpret_cast<f32x4 *>(x + i0) = v;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < total) x[i0 + j] = v[j];
+}
+
+// gp (N, L): the output gradient g (N, T = L - n) moved to the padded time axis and divided by the overlap-add envelope + eps - the
+// forward's own expression (ola_envelope: frames ascending, one fma per tap); 0 in the trimmed margins and where the denominator is 0
+__global__ __launch_bounds__(256) void istft_reim_prepare_kernel(const float *g, const float *win, float *gp, long long N, long long T, long long F,
+                                                                 int n, int hop, float eps, bool vec) {
+    const long long Lp = T + n, total = N * Lp;
+    const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= total) return;
+    long long clip = i0 / Lp, t = i0 - clip * Lp;
+    const int pad = n / 2;
+    f32x4 v;
+    if (t >= pad && t + 4 <= Lp - pad) {      // the interior of a clip: one 16-byte load (global loads only need 4-byte alignment)
+        const f32x4_u gv = *reinterpret_cast<const f32x4_u *>(g + clip * T + (t - pad));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float den = ola_envelope(win, t + j, n, hop, F) + eps;
+            v[j] = den != 0.f ? gv[j] / den : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float r = 0.f;
+            if (clip < N && t >= pad && t < Lp - pad) {
+                const float den = ola_envelope(win, t, n, hop, F) + eps;
+                if (den != 0.f) r = g[clip * T + (t - pad)] / den;
+            }
+            v[j] = r;
+            if (++t == Lp) t = 0, ++clip;
+        }
+    }
+    store_quad(gp, i0, total, vec, v);
+}
+
+struct ReimCombine {
+    const float *re, *im, *mask, *are, *aim;
+    float *g_re, *g_im, *g_mask;
+    long long total;      // N K F
+    int K, F, mask_kind;
+    float inv_n;
+    bool vec;
+};
+
+// (are, aim) = s_k (Re A, Im A) with aim = 0 at DC / Nyquist;  g_re = m are, g_im = m aim, g_mask = (re are + im aim) dm/dmask
+__global__ __launch_bounds__(256) void istft_reim_combine_kernel(ReimCombine p) {
+    const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i0 >= p.total) return;
+    const long long row0 = i0 / p.F;
+    int f = (int)(i0 - row0 * p.F), k = (int)(row0 % p.K);
+    f32x4 are = load_quad(p.are, i0, p.total, p.vec), aim = load_quad(p.aim, i0, p.total, p.vec);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool edge = k == 0 || k == p.K - 1;
+        const float s = edge ? p.inv_n : 2.f * p.inv_n;
+        are[j] *= s;
+        aim[j] = edge ? 0.f : aim[j] * s;
+        if (++f == p.F) f = 0, k = k + 1 == p.K ? 0 : k + 1;
+    }
+    f32x4 mk{0.f, 0.f, 0.f, 0.f};
+    if (p.mask_kind != PSND_MASK_NONE) mk = load_quad(p.mask, i0, p.total, p.vec);
+    if (p.g_re) {
+        f32x4 gr, gi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float m = reim_mask(p.mask_kind, mk[j]);
+            gr[j] = m * are[j], gi[j] = m * aim[j];
+        }
+        store_quad(p.g_re, i0, p.total, p.vec, gr);
+        store_quad(p.g_im, i0, p.total, p.vec, gi);
+    }
+    if (p.g_mask) {
+        const f32x4 re = load_quad(p.re, i0, p.total, p.vec), im = load_quad(p.im, i0, p.total, p.vec);
+        f32x4 gm;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            gm[j] = __builtin_fmaf(re[j], are[j], im[j] * aim[j]);
+            if (p.mask_kind == PSND_MASK_SIGMOID) {
+                const float sg = reim_mask(PSND_MASK_SIGMOID, mk[j]);
+                gm[j] *= sg * (1.f - sg);
+            }
+        }
+        store_quad(p.g_mask, i0, p.total, p.vec, gm);
+    }
+}
+
+inline size_t round4(size_t x) { return (x + 3) & ~(size_t)3; }
+inline bool aligned16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+}  // namespace
+
+extern "C" size_t psnd_istft_reim_bwd_scratch_bytes(int64_t N, int64_t F, int n_fft) {
+    if (N <= 0 || F <= 1 || (psnd_stft_plan_bytes(n_fft) == 0 && psnd_stft_mr_plan_bytes(n_fft) == 0)) return 0;
+    return sizeof(float) * (round4((size_t)N * (size_t)F * (size_t)n_fft) + 2 * round4((size_t)N * (size_t)(n_fft / 2 + 1) * (size_t)F));
+}
+
+extern "C" int psnd_istft_reim_bwd(const float *g, const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F,
+                                   int n_fft, int hop, const void *plan, size_t plan_bytes, float eps, void *scratch, size_t scratch_bytes,
+                                   float *g_re, float *g_im, float *g_mask, void *stream) {
+    if (!g || !plan) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: null g/plan");
+    if (mask_kind < PSND_MASK_NONE || mask_kind > PSND_MASK_SIGMOID || (mask != nullptr) != (mask_kind != PSND_MASK_NONE))
+        PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: mask_kind=%d with a %s mask", mask_kind, mask ? "non-NULL" : "NULL");
+    if ((g_re == nullptr) != (g_im == nullptr)) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: g_re and g_im must be given together");
+    if (!g_re && !g_mask) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: no output requested");
+    if (g_mask && !mask) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: g_mask without a mask");
+    if (g_mask && (!re || !im)) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: g_mask needs re and im");
+    if (hop <= 0 || N < 0 || F < 0) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: hop=%d N=%lld F=%lld", hop, (long long)N, (long long)F);
+    const size_t mr_bytes = psnd_stft_mr_plan_bytes(n_fft), p2_bytes = psnd_stft_plan_bytes(n_fft);
+    if (mr_bytes == 0 && p2_bytes == 0) PSND_FAIL(PSND_E_UNSUPPORTED, "istft_reim_bwd: n_fft=%d unsupported", n_fft);
+    if (plan_bytes != (mr_bytes ? mr_bytes : p2_bytes))
+        PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: a plan of %zu bytes is not the plan of n_fft=%d (%zu bytes)", plan_bytes, n_fft,
+                  mr_bytes ? mr_bytes : p2_bytes);
+    if (hop > n_fft) PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: hop=%d exceeds n_fft=%d", hop, n_fft);
+    if (N == 0 || F <= 1) return PSND_OK;
+    const int64_t K = n_fft / 2 + 1, T = (F - 1) * hop, Lp = T + n_fft;
+    if (K * F >= (int64_t)1 << 31 || Lp >= ((int64_t)1 << 31) - 4 * (int64_t)n_fft) PSND_FAIL(PSND_E_SHAPE, "istft_reim_bwd: clip too long");
+    const size_t need = psnd_istft_reim_bwd_scratch_bytes(N, F, n_fft);
+    if (!scratch || scratch_bytes < need)
+        PSND_FAIL(PSND_E_ARG, "istft_reim_bwd: scratch of %zu bytes, psnd_istft_reim_bwd_scratch_bytes asks for %zu", scratch ? scratch_bytes : (size_t)0,
+                  need);
+    const size_t nkf = (size_t)N * (size_t)K * (size_t)F, npl = (size_t)N * (size_t)Lp;
+    const size_t quads_p = (npl + 3) / 4, quads_c = (nkf + 3) / 4;
+    if ((quads_p + 255) / 256 > 0x7fffffff || (quads_c + 255) / 256 > 0x7fffffff) PSND_FAIL(PSND_E_SHAPE, "istft_reim_bwd: grid too large");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *are = static_cast<float *>(scratch), *aim = are + round4(nkf), *gp = aim + round4(nkf);      // gp: N Lp <= N F n_fft floats
+    const float *win;
+    if (mr_bytes) {
+        win = psnd_stft_mr_plan_window(plan);
+    } else {
+        const Decomp *d = find_decomp(n_fft);
+        win = static_cast<const float *>(plan) + (d ? plan_layout(n_fft, d->R1, d->L).win : 0);
+    }
+    hipLaunchKernelGGL(istft_reim_prepare_kernel, dim3((unsigned)((quads_p + 255) / 256)), dim3(256), 0, s, g, win, gp, (long long)N, (long long)T,
+                       (long long)F, n_fft, hop, eps, aligned16(gp));
+    PSND_CHECK_LAUNCH("istft_reim_bwd(prepare)");
+    const int rc = mr_bytes ? psnd_stft_mr_fwd(gp, N, Lp, n_fft, hop, PSND_FRAMING_NONE, plan, plan_bytes, 0.f, nullptr, nullptr, are, aim, stream)
+                            : psnd_stft_fwd(gp, N, Lp, n_fft, hop, PSND_FRAMING_NONE, plan, 0.f, nullptr, nullptr, are, aim, stream);
+    if (rc != PSND_OK) return rc;
+    ReimCombine c;
+    c.re = re, c.im = im, c.mask = mask, c.are = are, c.aim = aim, c.g_re = g_re, c.g_im = g_im, c.g_mask = g_mask;
+    c.total = (long long)nkf, c.K = (int)K, c.F = (int)F, c.mask_kind = mask_kind, c.inv_n = 1.0f / (float)n_fft;
+    c.vec = aligned16(are) && aligned16(aim) && aligned16(re) && aligned16(im) && aligned16(mask) && aligned16(g_re) && aligned16(g_im) &&
+            aligned16(g_mask);
+    hipLaunchKernelGGL(istft_reim_combine_kernel, dim3((unsigned)((quads_c + 255) / 256)), dim3(256), 0, s, c);
+    PSND_CHECK_LAUNCH("istft_reim_bwd(combine)");
     return PSND_OK;
 }

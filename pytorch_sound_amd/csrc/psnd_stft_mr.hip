@@ -53,11 +53,12 @@ struct MrParams {
     const float *wav;
     const float *plan;
     float *mag, *phase, *re, *im;        // forward outputs (any subset)
-    const float *gmag, *gre, *gim;       // backward sources; inverse: gmag = magnitude, gre = phase
+    const float *gmag, *gre, *gim;       // backward sources; inverse: gmag = magnitude, gre = phase; on (re, im): gmag = re, gre = im, gim = mask
     float *scratch;                      // (N, F, n) windowed frames of the backward / inverse
     long long T, F;
     int n, hop, pad;
     float mag_eps, inv_n;
+    int mask_kind;                       // PSND_MASK_* of the inverse on (re, im)
     int npass;
     int radix[kMrMaxPass];
 };
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(kMrThreads) void stft_mr_fwd_kernel(MrParams p) {
 // ---------------------------------------------------------------------------------------------
 // backward / inverse, launch 1: window * (adjoint or inverse real DFT) of every frame -> scratch (N, F, n)
 // ---------------------------------------------------------------------------------------------
-enum { MR_FROM_MAG = 1, MR_FROM_REIM = 2, MR_ISTFT = 4 };
+enum { MR_FROM_MAG = 1, MR_FROM_REIM = 2, MR_ISTFT = 4, MR_ISTFT_REIM = 8 };   // MR_ISTFT_REIM rides on MR_ISTFT: the (re, im) loader
 
 template <int MODE>
 __global__ __launch_bounds__(kMrThreads) void stft_mr_frames_kernel(MrParams p) {
@@ -276,7 +277,14 @@ __global__ __launch_bounds__(kMrThreads) void stft_mr_frames_kernel(MrParams p) 
                 gar += p.gre[o], gai += p.gim[o];
                 if (has_b) gbr += p.gre[o + 1], gbi += p.gim[o + 1];
             }
-            if constexpr ((MODE & MR_ISTFT) != 0) {      // X / n; the Hermitian extension below supplies the factor two of the interior bins
+            if constexpr ((MODE & MR_ISTFT_REIM) != 0) {  // X = m (re + i im), scaled as below
+                const float ma = reim_mask(p.mask_kind, p.gim ? p.gim[o] : 1.f) * p.inv_n;
+                gar = ma * p.gmag[o], gai = ma * p.gre[o];
+                if (has_b) {
+                    const float mb = reim_mask(p.mask_kind, p.gim ? p.gim[o + 1] : 1.f) * p.inv_n;
+                    gbr = mb * p.gmag[o + 1], gbi = mb * p.gre[o + 1];
+                }
+            } else if constexpr ((MODE & MR_ISTFT) != 0) {      // X / n; the Hermitian extension below supplies the factor two of the interior bins
                 float sn, cs;
                 sincosf(p.gre[o], &sn, &cs);
                 const float ma = p.gmag[o] * p.inv_n;
@@ -352,6 +360,8 @@ void mr_fill(MrParams &p, int n_fft, const void *plan) {
 }
 
 }  // namespace
+
+const float *psnd_stft_mr_plan_window(const void *plan) { return static_cast<const float *>(plan) + kMrHeader; }
 
 extern "C" size_t psnd_stft_mr_plan_bytes(int n_fft) {
     return mr_covered(n_fft) ? sizeof(float) * (size_t)(kMrHeader + 3 * n_fft) : 0;
@@ -464,28 +474,43 @@ extern "C" size_t psnd_istft_mr_scratch_bytes(int64_t N, int64_t F, int n_fft) {
     return sizeof(float) * (size_t)N * (size_t)F * (size_t)n_fft;
 }
 
-extern "C" int psnd_istft_mr(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop, const void *plan, size_t plan_bytes,
-                             float eps, void *scratch, size_t scratch_bytes, float *out, void *stream) {
-    if (!mag || !phase || !plan || !out) PSND_FAIL(PSND_E_ARG, "istft_mr: null pointer");
-    if (hop <= 0 || N < 0 || F < 0) PSND_FAIL(PSND_E_ARG, "istft_mr: hop=%d N=%lld F=%lld", hop, (long long)N, (long long)F);
+// REIM: (a, b) = (re, im) with an optional mask instead of (magnitude, phase) - psnd_istft_reim_mr
+template <bool REIM>
+static int istft_mr_impl(const char *what, const float *a, const float *b, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft, int hop,
+                         const void *plan, size_t plan_bytes, float eps, void *scratch, size_t scratch_bytes, float *out, void *stream) {
+    if (!a || !b || !plan || !out) PSND_FAIL(PSND_E_ARG, "%s: null pointer", what);
+    if (REIM && (mask_kind < PSND_MASK_NONE || mask_kind > PSND_MASK_SIGMOID || (mask != nullptr) != (mask_kind != PSND_MASK_NONE)))
+        PSND_FAIL(PSND_E_ARG, "%s: mask_kind=%d with a %s mask", what, mask_kind, mask ? "non-NULL" : "NULL");
+    if (hop <= 0 || N < 0 || F < 0) PSND_FAIL(PSND_E_ARG, "%s: hop=%d N=%lld F=%lld", what, hop, (long long)N, (long long)F);
     const int64_t T = F > 0 ? (F - 1) * hop : 0;
-    const int rc = mr_check("istft_mr", N, T, F, n_fft, plan_bytes);
+    const int rc = mr_check(what, N, T, F, n_fft, plan_bytes);
     if (rc != PSND_OK) return rc;
     if (N == 0 || F <= 1) return PSND_OK;
     const size_t need = psnd_istft_mr_scratch_bytes(N, F, n_fft);
     if (!scratch || scratch_bytes < need)
-        PSND_FAIL(PSND_E_ARG, "istft_mr: scratch of %zu bytes, psnd_istft_mr_scratch_bytes asks for %zu", scratch ? scratch_bytes : (size_t)0, need);
+        PSND_FAIL(PSND_E_ARG, "%s: scratch of %zu bytes, psnd_istft_mr_scratch_bytes asks for %zu", what, scratch ? scratch_bytes : (size_t)0, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
     MrParams p;
     mr_fill(p, n_fft, plan);
-    p.gmag = mag, p.gre = phase, p.scratch = static_cast<float *>(scratch);
+    p.gmag = a, p.gre = b, p.gim = mask, p.mask_kind = mask_kind, p.scratch = static_cast<float *>(scratch);
     p.T = T, p.F = F, p.hop = hop, p.pad = n_fft / 2;
     const dim3 grid((unsigned)((F + kMrTile - 1) / kMrTile), (unsigned)N);
-    hipLaunchKernelGGL((stft_mr_frames_kernel<MR_ISTFT>), grid, dim3(kMrThreads), sizeof(float) * 2 * (size_t)n_fft, s, p);
-    PSND_CHECK_LAUNCH("istft_mr(frames)");
+    hipLaunchKernelGGL((stft_mr_frames_kernel<REIM ? (MR_ISTFT | MR_ISTFT_REIM) : MR_ISTFT>), grid, dim3(kMrThreads), sizeof(float) * 2 * (size_t)n_fft, s, p);
+    PSND_CHECK_LAUNCH(REIM ? "istft_reim_mr(frames)" : "istft_mr(frames)");
     const dim3 ggrid((unsigned)((T + kMrThreads - 1) / kMrThreads), (unsigned)N);
     hipLaunchKernelGGL((stft_mr_gather_kernel<true>), ggrid, dim3(kMrThreads), 0, s, p.scratch, p.plan + kMrHeader, out, (long long)T, (long long)F, n_fft,
                        hop, n_fft / 2, eps);
-    PSND_CHECK_LAUNCH("istft_mr(gather)");
+    PSND_CHECK_LAUNCH(REIM ? "istft_reim_mr(gather)" : "istft_mr(gather)");
     return PSND_OK;
+}
+
+extern "C" int psnd_istft_mr(const float *mag, const float *phase, int64_t N, int64_t F, int n_fft, int hop, const void *plan, size_t plan_bytes,
+                             float eps, void *scratch, size_t scratch_bytes, float *out, void *stream) {
+    return istft_mr_impl<false>("istft_mr", mag, phase, nullptr, PSND_MASK_NONE, N, F, n_fft, hop, plan, plan_bytes, eps, scratch, scratch_bytes, out,
+                                stream);
+}
+
+extern "C" int psnd_istft_reim_mr(const float *re, const float *im, const float *mask, int mask_kind, int64_t N, int64_t F, int n_fft, int hop,
+                                  const void *plan, size_t plan_bytes, float eps, void *scratch, size_t scratch_bytes, float *out, void *stream) {
+    return istft_mr_impl<true>("istft_reim_mr", re, im, mask, mask_kind, N, F, n_fft, hop, plan, plan_bytes, eps, scratch, scratch_bytes, out, stream);
 }

@@ -63,8 +63,33 @@ def istft(magnitude, phase, n_fft, hop, window, eps=1e-9):
     if K != n_fft // 2 + 1 or phase.shape != magnitude.shape:
         raise RuntimeError('istft: expected (N, %d, F) magnitude and phase, got %s / %s'
                            % (n_fft // 2 + 1, tuple(magnitude.shape), tuple(phase.shape)))
-    w = window.to(magnitude.dtype)
-    fr = torch.fft.irfft(torch.polar(magnitude, phase), n=n_fft, dim=1) * w.view(1, -1, 1)       # (N, n, F)
+    return _istft_of(torch.polar(magnitude, phase), n_fft, hop, window.to(magnitude.dtype), eps)
+
+
+MASK_NONE, MASK_LINEAR, MASK_SIGMOID = 0, 1, 2
+
+
+def istft_complex(re, im, mask, mask_kind, n_fft, hop, window, eps=1e-9):
+    """istft of the spectrum m (re + i im) without the polar round trip: m = 1 (MASK_NONE, mask None), the mask (MASK_LINEAR) or
+    sigmoid(mask) (MASK_SIGMOID).  mask |X| e^{i arg X} is mask X, so this is STFT.inverse(mask * mag, phase) of X = re + i im."""
+    _check_host(re, 're')
+    N, K, Fr = re.shape
+    if K != n_fft // 2 + 1 or im.shape != re.shape:
+        raise RuntimeError('istft_complex: expected (N, %d, F) re and im, got %s / %s' % (n_fft // 2 + 1, tuple(re.shape), tuple(im.shape)))
+    if mask_kind is None:
+        mask_kind = MASK_NONE if mask is None else MASK_LINEAR
+    if mask_kind not in (MASK_NONE, MASK_LINEAR, MASK_SIGMOID) or (mask is None) != (mask_kind == MASK_NONE):
+        raise RuntimeError('istft_complex: mask_kind=%r %s a mask' % (mask_kind, 'without' if mask is None else 'with'))
+    if mask_kind != MASK_NONE:
+        m = torch.sigmoid(mask) if mask_kind == MASK_SIGMOID else mask
+        re, im = m * re, m * im
+    return _istft_of(torch.complex(re, im), n_fft, hop, window.to(re.dtype), eps)
+
+
+def _istft_of(spec, n_fft, hop, w, eps):
+    """overlap-add of window * irfft(spec) over the frames, divided by the squared-window envelope + eps, n/2 trimmed on both sides"""
+    N, _, Fr = spec.shape
+    fr = torch.fft.irfft(spec, n=n_fft, dim=1) * w.view(1, -1, 1)       # (N, n, F)
     L = n_fft + hop * (Fr - 1)
     ola = F.fold(fr, (1, L), (1, n_fft), stride=(1, hop)).reshape(N, L)
     env = F.fold((w * w).view(1, -1, 1).expand(1, n_fft, Fr).contiguous(), (1, L), (1, n_fft), stride=(1, hop)).reshape(L)

@@ -476,6 +476,99 @@ def istft(magnitude, phase, n_fft, hop, plan, eps=1e-9, window=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# masked inverse STFT on (re, im): psnd_istft_reim / _reim_mr / _reim_bwd
+# ---------------------------------------------------------------------------------------------
+MASK_NONE, MASK_LINEAR, MASK_SIGMOID = _lib.MASK_NONE, _lib.MASK_LINEAR, _lib.MASK_SIGMOID
+
+
+def _reim_args(re, im, mask, mask_kind, n_fft):
+    _need_cuda(re, 're')
+    _need_cuda(im, 'im')
+    if re.dim() != 3 or re.shape[1] != n_fft // 2 + 1 or im.shape != re.shape:
+        raise _lib.PsndError('istft_reim: expected (N, %d, F) re and im, got %s / %s' % (n_fft // 2 + 1, tuple(re.shape), tuple(im.shape)))
+    if mask_kind not in (MASK_NONE, MASK_LINEAR, MASK_SIGMOID) or (mask is None) != (mask_kind == MASK_NONE):
+        raise _lib.PsndError('istft_reim: mask_kind=%r %s a mask' % (mask_kind, 'without' if mask is None else 'with'))
+    if mask is not None:
+        _need_cuda(mask, 'mask')
+        if mask.shape != re.shape:
+            raise _lib.PsndError('istft_reim: mask %s does not match the spectrum %s' % (tuple(mask.shape), tuple(re.shape)))
+        mask = mask.contiguous()
+    return re.contiguous(), im.contiguous(), mask
+
+
+def istft_reim_forward(re, im, mask, mask_kind, n_fft, hop, plan, eps=1e-9):
+    """the waveform of the spectrum m (re + i im), (N, (F - 1) hop): psnd_istft's definition without the polar round trip"""
+    re, im, mask = _reim_args(re, im, mask, mask_kind, n_fft)
+    N, _, F = re.shape
+    out = torch.empty((N, max((F - 1) * hop, 0)), dtype=torch.float32, device=re.device)
+    with torch.cuda.device(re.device):
+        if stft_plan_kind(plan, n_fft) == PLAN_MR:
+            nb = int(lib().psnd_istft_mr_scratch_bytes(N, F, n_fft))
+            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=re.device)
+            check(lib().psnd_istft_reim_mr(ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
+                                           ptr(scratch), scratch.numel() * 4, ptr(out), stream_ptr(re.device)), 'psnd_istft_reim_mr')
+            return out
+        check(lib().psnd_istft_reim(ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), float(eps), ptr(out),
+                                    stream_ptr(re.device)), 'psnd_istft_reim')
+    return out
+
+
+def istft_reim_backward(g, re, im, mask, mask_kind, n_fft, hop, plan, eps=1e-9, want_reim=True, want_mask=True):
+    """(g_re, g_im, g_mask) of istft_reim_forward for the output gradient g, each (N, K, F) or None: three launches (psnd_istft_reim_bwd)"""
+    re, im, mask = _reim_args(re, im, mask, mask_kind, n_fft)
+    _need_cuda(g, 'g')
+    g = g.contiguous()
+    N, _, F = re.shape
+    if tuple(g.shape) != (N, max((F - 1) * hop, 0)):
+        raise _lib.PsndError('istft_reim_backward: g %s is not the (N, (F - 1) hop) = (%d, %d) output gradient' % (tuple(g.shape), N, (F - 1) * hop))
+    want_mask = want_mask and mask is not None
+    # F <= 1: the output is empty and the entry point launches nothing, so the gradients are allocated as zeros
+    mk = torch.zeros_like if F <= 1 or N == 0 else torch.empty_like
+    g_re = mk(re) if want_reim else None
+    g_im = mk(re) if want_reim else None
+    g_mask = mk(re) if want_mask else None
+    if not want_reim and not want_mask:
+        return None, None, None
+    nb = int(lib().psnd_istft_reim_bwd_scratch_bytes(N, F, n_fft))
+    scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=re.device)
+    with torch.cuda.device(re.device):
+        check(lib().psnd_istft_reim_bwd(ptr(g), ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
+                                        ptr(scratch), scratch.numel() * 4, ptr(g_re), ptr(g_im), ptr(g_mask), stream_ptr(re.device)),
+              'psnd_istft_reim_bwd')
+    return g_re, g_im, g_mask
+
+
+class IStftReIm(torch.autograd.Function):
+    """istft_reim: the inverse STFT of m (re + i im).  Both directions are kernels of the library - inside this node no ATen compute op
+    touches a HIP tensor, only allocations."""
+
+    @staticmethod
+    def forward(ctx, re, im, mask, plan, mask_kind, n_fft, hop, eps):
+        out = istft_reim_forward(re, im, mask, mask_kind, n_fft, hop, plan, eps)
+        ctx.save_for_backward(re, im, mask, plan)
+        ctx.cfg = (mask_kind, n_fft, hop, eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        re, im, mask, plan = ctx.saved_tensors
+        mask_kind, n_fft, hop, eps = ctx.cfg
+        need = ctx.needs_input_grad
+        g_re, g_im, g_mask = istft_reim_backward(g, re, im, mask, mask_kind, n_fft, hop, plan, eps, need[0] or need[1], need[2])
+        return (g_re if need[0] else None), (g_im if need[1] else None), g_mask, None, None, None, None, None
+
+
+def istft_reim(re, im, mask, mask_kind, n_fft, hop, plan, eps=1e-9):
+    """waveform (N, (F - 1) hop) of the spectrum m (re + i im); m = 1 (MASK_NONE, mask None), the mask (MASK_LINEAR) or sigmoid(mask)
+    (MASK_SIGMOID, evaluated in the kernel).  Differentiable in re, im and mask; the plan kind is told by stft_plan_kind."""
+    if mask_kind is None:
+        mask_kind = MASK_NONE if mask is None else MASK_LINEAR
+    if torch.is_grad_enabled() and (re.requires_grad or im.requires_grad or (mask is not None and mask.requires_grad)):
+        return IStftReIm.apply(re, im, mask, plan, mask_kind, n_fft, hop, eps)
+    return istft_reim_forward(re, im, mask, mask_kind, n_fft, hop, plan, eps)
+
+
+# ---------------------------------------------------------------------------------------------
 # transformer blocks (models/modules.py): GroupNorm(1, C)(x + res) and the masked softmax over keys
 # ---------------------------------------------------------------------------------------------
 RESIDUAL_LINKS = _sw.lab('PSND_RESIDUAL_LINKS', '1') == '1'      # 0: autograd accumulates the two gradients of a block's input (A/B)

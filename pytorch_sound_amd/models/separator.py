@@ -45,11 +45,54 @@ class ConvSeparator(nn.Module):
         return self._forward_plain(mag)
 
     def _forward_plain(self, mag):
+        return torch.sigmoid(self._logits_plain(mag)) * mag
+
+    def _logits_plain(self, mag):
         x = self.conv_pre(torch.log1p(mag))
         for block in self.blocks:
             x = block(x)
-        mask = torch.sigmoid(self.conv_post(x, LRELU_SLOPE))
-        return mask * mag
+        return self.conv_post(x, LRELU_SLOPE)
+
+    def mask_logits(self, mag: torch.Tensor) -> torch.Tensor:
+        """the mask logits (N, K, F) fp32 - forward() without its head sigmoid(.) * mag.  HIP tensor under bf16 (wants_bf16): the
+        channels-last body (logits_cl) and one layout change back; otherwise the plain convolutions."""
+        from pytorch_sound_amd import deferred
+        mag = deferred.resolve(mag)
+        if mag.is_cuda and wants_bf16(self.precision, mag):
+            from pytorch_sound_amd import cl
+            N, C, T = mag.shape
+            y, shape = self.logits_cl(mag)
+            return cl.FromCL.apply(y, C, T, shape)
+        if mag.is_cuda:
+            with torch.autocast('cuda', enabled=False):
+                return self._logits_plain(mag.float())
+        return self._logits_plain(mag).float()
+
+    def separate(self, wav: torch.Tensor, stft, eps: float = None) -> torch.Tensor:
+        """mixture waveform (N, T) -> separated waveform (N, (F - 1) hop): one STFT launch gives |X|, Re X and Im X of the mixture, the
+        model gives mask logits, and the inverse STFT of sigmoid(logits) X (kernels.istft_reim: sigmoid and product inside the kernel,
+        no magnitude-times-mask tensor, no phase) gives the audio.  Differentiable in the parameters; the mixture carries no gradient.
+        `stft`: an STFT or an STFTTorchAudio; eps defaults to that class's convention (1e-9 / 0).  No host synchronisation."""
+        from pytorch_sound_amd import host as H, kernels as K
+        from pytorch_sound_amd.models.transforms import STFTTorchAudio
+        if wav.dim() != 2:
+            raise RuntimeError('expected a (N, T) waveform batch, got shape %s' % (tuple(wav.shape),))
+        if torch.is_grad_enabled() and wav.requires_grad:
+            raise RuntimeError('ConvSeparator.separate: the mixture carries no gradient (wav.requires_grad is set)')
+        torchaudio_kind = isinstance(stft, STFTTorchAudio)
+        n_fft = stft.n_fft if torchaudio_kind else stft.filter_length
+        hop = stft.hop_length
+        if eps is None:
+            eps = 0.0 if torchaudio_kind else 1e-9
+        if not wav.is_cuda:
+            c = H.stft_complex(wav, n_fft, hop, stft._host_window(), H.FRAMING_CENTER)
+            re, im = c.real, c.imag
+            logits = self.mask_logits(torch.sqrt(re ** 2 + im ** 2))
+            return H.istft_complex(re, im, logits, H.MASK_SIGMOID, n_fft, hop, stft._host_window(), eps)
+        plan = stft._plan(wav.device)
+        o = K.stft_forward(wav.detach().float(), n_fft, hop, plan, K.FRAMING_CENTER, 0.0, want_mag=True, want_reim=True)
+        logits = self.mask_logits(o['mag'])
+        return K.istft_reim(o['re'], o['im'], logits, K.MASK_SIGMOID, n_fft, hop, plan, eps)
 
 
     def logits_cl(self, mag: torch.Tensor, layout: str = 'nkf'):

@@ -4,6 +4,7 @@ pytorch_sound/models/transforms.py, computed by the gfx950 kernels of libpsnd_hi
 Reference            here                                   kernel(s)
 STFT.transform       STFT.transform -> (mag, phase)         psnd_stft_fwd / psnd_stft_bwd
 STFT.inverse         STFT.inverse                           psnd_istft
+(none)               STFT / STFTTorchAudio.inverse_complex  psnd_istft_reim / _reim_mr / _reim_bwd
 LogMelSpectrogram    LogMelSpectrogram.forward              psnd_stft_fwd + psnd_mel_fwd (+ bwd)
 STFTTorchAudio       forward -> (re, im); transform         psnd_stft_fwd(re,im) / psnd_stft_bwd
 Audio2Mel            forward (N,1,T) -> log10 mel           psnd_stft_fwd(HIFIGAN) + psnd_mel_fwd
@@ -142,6 +143,24 @@ class STFT(nn.Module):
         win = self._plans.get('win', magnitude.device, lambda: torch.from_numpy(self._window_np))
         return K.istft(magnitude, phase, self.filter_length, self.hop_length, self._plan(magnitude.device), eps, win)
 
+    def transform_complex(self, wav: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(N,T) -> real, imag of the same spectrum transform() describes as (magnitude, phase), both differentiable.  On a HIP tensor
+        every size K.stft_plan covers (powers of two and the mixed-radix sizes) takes the STFT kernels; any other size raises."""
+        wav = _as_2d(wav)
+        if not wav.is_cuda:
+            c = H.stft_complex(wav, self.filter_length, self.hop_length, self._host_window(), H.FRAMING_CENTER)
+            return c.real, c.imag
+        return K.StftReIm.apply(wav, self._plan(wav.device), self.filter_length, self.hop_length, K.FRAMING_CENTER)
+
+    def inverse_complex(self, real: torch.Tensor, imag: torch.Tensor, mask: torch.Tensor = None, mask_kind: int = None,
+                        eps: float = 1e-9) -> torch.Tensor:
+        """inverse() of the spectrum m (real + i imag) without magnitude and phase: m = 1 without a mask, the mask itself
+        (K.MASK_LINEAR, the default with a mask) or sigmoid(mask) of mask logits (K.MASK_SIGMOID).  Native in both directions on a HIP
+        tensor (psnd_istft_reim*), for every size K.stft_plan covers; any other size raises."""
+        if not real.is_cuda:
+            return H.istft_complex(real, imag, mask, mask_kind, self.filter_length, self.hop_length, self._host_window(), eps)
+        return K.istft_reim(real, imag, mask, mask_kind, self.filter_length, self.hop_length, self._plan(real.device), eps)
+
     def forward(self, wav: torch.Tensor) -> torch.Tensor:  # the reference defines no forward
         raise NotImplementedError
 
@@ -276,6 +295,13 @@ class STFTTorchAudio(nn.Module):
         win = self._plans.get(('win', w._version, w.data_ptr()), magnitude.device, lambda: torch.from_numpy(
             centre_pad(w.detach().cpu().numpy().astype(np.float32), self.n_fft)))
         return K.istft(magnitude, phase, self.n_fft, self.hop_length, self._plan(magnitude.device), 0.0, win)
+
+    def inverse_complex(self, real: torch.Tensor, imag: torch.Tensor, mask: torch.Tensor = None, mask_kind: int = None) -> torch.Tensor:
+        """inverse() of the spectrum m (real + i imag) - what forward() returns, optionally masked (STFT.inverse_complex) - with
+        torch.istft's eps = 0"""
+        if not real.is_cuda:
+            return H.istft_complex(real, imag, mask, mask_kind, self.n_fft, self.hop_length, self._host_window(), 0.0)
+        return K.istft_reim(real, imag, mask, mask_kind, self.n_fft, self.hop_length, self._plan(real.device), 0.0)
 
 
 class _HifiGanMel(nn.Module):
