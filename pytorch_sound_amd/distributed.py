@@ -131,7 +131,9 @@ class FlatGradReducer:
         self._events = None
         self._side = None
         self.release_marks = []      # (tests) per bucket: timing event recorded on the side stream when its wait was released
-        self.params: List[torch.nn.Parameter] = [p for p in module.parameters() if p.requires_grad]
+        self._all_params = list(module.parameters())      # check_trainable: the requires_grad bits the layout below was made for
+        self._trainable_bits = [p.requires_grad for p in self._all_params]
+        self.params: List[torch.nn.Parameter] = [p for p in self._all_params if p.requires_grad]
         self.buckets = []            # dicts: flat, params, pending, work
         self._next = 0               # first bucket whose all-reduce has not been issued in this step
         self.launch_log = collections.deque(maxlen=4096)   # bucket indices in the order their collectives were issued (tests)
@@ -327,8 +329,20 @@ class FlatGradReducer:
         finally:
             self._in_deliver = 0
 
+    def check_trainable(self):
+        """the buckets, slots and hooks were laid out for the parameters that required a gradient at construction: a parameter unfrozen
+        since has no slot, one frozen since would leave its bucket waiting and be stepped with a zero gradient (Adam still moves it:
+        momentum, weight decay).  Rebuilding buckets mid-run is not done here - the caller builds a new reducer."""
+        now = [p.requires_grad for p in self._all_params]
+        if now != self._trainable_bits:
+            from ._lib import PsndError
+            raise PsndError('FlatGradReducer: the set of trainable parameters changed since it was built (%d parameters required a '
+                            'gradient then, %d do now) - remove() this reducer and build a new one after freezing or unfreezing'
+                            % (len(self.params), sum(now)))
+
     # gradients must stay views of the flat buffers: zero in place instead of dropping them
     def zero_grad(self):
+        self.check_trainable()
         self._next = 0
         self._sunk.clear()
         self._delivered.clear()

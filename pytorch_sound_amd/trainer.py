@@ -142,6 +142,13 @@ class _GeneratorWatch(torch.overrides.TorchFunctionMode):
         return func(*args, **kwargs)
 
 
+def model_fingerprint(params, modules) -> tuple:
+    """what a captured training step froze of the model's own state: the `requires_grad` bit of every parameter and the `training` bit of
+    every module, in the order given (`parameters()` / `modules()` order).  Values and gradients do not enter; a different NUMBER of either
+    compares unequal like any other difference"""
+    return tuple(p.requires_grad for p in params), tuple(m.training for m in modules)
+
+
 def dist_backend_is_nccl() -> bool:
     return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_backend() == 'nccl'
 
@@ -333,6 +340,48 @@ class Trainer:
             with torch.no_grad():
                 meta = {k: (resolve(v[0]), *v[1:]) if isinstance(v, tuple) and v else v for k, v in meta.items()}
         return loss, meta
+
+    # ---- the model's own state under captured steps ---------------------------------------------------------
+    # A captured step repeats what Python decided while it was captured: which parameters get a gradient (`requires_grad`) and which
+    # branch a module takes (`module.training`: the dropout inside the GroupNorm kernels).  So the graphs are keyed on the batch signature
+    # AND on model_fingerprint(): every train() call compares the fingerprint (two tuple builds over lists cached here, ~30 us for
+    # HiFi-GAN v1) with the one the graphs were captured under, and a difference drops them - the signatures warm up and are captured
+    # again, graph_steps = 'auto' stays on.  The cached lists are walked afresh (~270 us) on logging steps only, so a module or parameter
+    # added to the model is seen at the next logging step.  Edits the fingerprint cannot see - plain attributes read in Python
+    # (`cl_upsample`, `return_att`, a dropout rate) - need reset_graphs().
+    _model_fp = None
+    _model_lists_cache = None
+
+    def _model_lists(self, refresh: bool = False):
+        if refresh or self._model_lists_cache is None:
+            m = self._bare_model
+            self._model_lists_cache = (list(m.parameters()), list(m.modules()))
+        return self._model_lists_cache
+
+    def _check_model_state(self, refresh: bool = False):
+        """top of every train() call: graphs captured under another fingerprint go (reset_graphs)"""
+        fp = model_fingerprint(*self._model_lists(refresh))
+        if fp != self._model_fp:
+            changed = self._model_fp is not None
+            self.reset_graphs()
+            if changed:
+                self._log('the model changed (requires_grad / train-eval flags): captured steps are dropped and captured again')
+
+    def reset_graphs(self):
+        """forget every captured step and its warm-up count (after a synchronize), set `.grad = None` on every parameter that does not
+        require a gradient, look at the optimizer's coverage again; the next steps run eagerly, warm up and are captured as at the start.
+        Called by train() when model_fingerprint() changed; call it yourself after an edit the fingerprint cannot see."""
+        if any('graph' in v for v in getattr(self, '_graphs', {}).values()):
+            torch.cuda.synchronize()                     # no replay of them still in flight
+        self._graphs = {}
+        params, modules = self._model_lists(refresh=True)
+        self._model_fp = model_fingerprint(params, modules)
+        for p in params:
+            if not p.requires_grad:
+                p.grad = None                            # (a dropped graph's static gradient, a bucket view, a backward from before the freeze)
+        self._opt_cover = None
+        if getattr(self, '_reducer', None) is not None:
+            self._reducer.check_trainable()              # raises: its buckets were laid out for another trainable set
 
     def _stay_eager(self, why: str):
         """graph_steps = 'auto' after a forward() that made a host-side decision: no capture from now on, and graphs captured before it (the
@@ -1003,6 +1052,7 @@ class Trainer:
     def train(self, step: int):
         self._maybe_freeze_gc()
         log_flag = step % self.log_interval == 0
+        self._check_model_state(refresh=log_flag)      # (a logging step walks the model again: a module added to it)
         batch = self._take_train_batch()
         self._maybe_adopt_optimizer()
         use_graph = self.graph_steps is True or (self.graph_steps == 'auto' and self._graph_auto_ok is not False and self._reducer is None)

@@ -295,3 +295,109 @@ def test_seed_broadcast_and_fixed_collective_order(tmp_path):
     assert res[0][1] == res[1][1] == list(range(nb)) * 3             # every step: buckets 0..nb-1 in order on both ranks
     for k in res[0][3]:
         assert np.array_equal(res[0][3][k], res[1][3][k]), k
+
+
+# ---- frozen parameters -----------------------------------------------------------------------------------------------------------------
+def _frozen_worker(rank, world, port, tmp, q, toggle):
+    """toggle None: two parameters frozen BEFORE the Trainer (and its reducer) is built, four Adam steps.  'freeze' / 'unfreeze': the
+    trainable set changes after step 2 - the reducer refuses the next step on both ranks"""
+    sys.path.insert(0, ROOT)
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), LOCAL_RANK=str(rank))
+    torch.cuda.is_available = lambda: False
+    import torch.distributed as dist
+    from pytorch_sound_amd import distributed as pdist
+    from pytorch_sound_amd._lib import PsndError
+    from pytorch_sound_amd.trainer import Trainer, LogType
+    assert pdist.init_from_env('gloo')
+
+    class T(Trainer):
+        def forward(self, x, y, is_logging=False):
+            loss = torch.nn.functional.mse_loss(self.model(x), y)
+            return loss, {'loss': (loss.item(), LogType.SCALAR)}
+
+    net = _net()
+    net[0].weight.requires_grad_(False)
+    net[2].bias.requires_grad_(False)
+    data = _batches(6)
+    mine = [(x[rank * 2:rank * 2 + 2], y[rank * 2:rank * 2 + 2]) for x, y in data]
+    opt = torch.optim.Adam(net.parameters(), lr=0.05, weight_decay=0.01)      # frozen ones included: a zero gradient would still move them
+    tr = T(net, opt, mine, mine[:1], max_step=4, valid_max_step=1, save_interval=10 ** 6, log_interval=10 ** 6, save_dir=tmp,
+           save_prefix='fz', seed=3)
+    assert len(tr._reducer.params) == 2
+    net.train()
+    err, none_ok = None, True
+    for i in range(1, 5):
+        if i == 3 and toggle == 'freeze':
+            net[0].bias.requires_grad_(False)
+        if i == 3 and toggle == 'unfreeze':
+            net[2].bias.requires_grad_(True)
+        tr.step = i
+        try:
+            tr.train(i)
+        except PsndError as e:
+            err = (i, str(e))
+            break
+        none_ok = none_ok and all(p.grad is None for p in net.parameters() if not p.requires_grad)
+    q.put((rank, {k: v.numpy() for k, v in net.state_dict().items()}, err, none_ok))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _run_frozen(tmp_path, toggle):
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_frozen_worker, args=(r, 2, port, str(tmp_path), q, toggle)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = {}
+    for _ in range(2):
+        r, sd, err, none_ok = q.get(timeout=240)
+        res[r] = (sd, err, none_ok)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    return res
+
+
+@pytest.mark.timeout(300)
+def test_two_rank_gloo_training_with_frozen_parameters(tmp_path):
+    """parameters frozen before the reducer is built have no slot, get no gradient and stay bit for bit where they were; the others train
+    like one float64 process on the concatenated batch"""
+    res = _run_frozen(tmp_path, None)
+    for k in res[0][0]:
+        assert np.array_equal(res[0][0][k], res[1][0][k]), k
+    assert res[0][1] is None and res[1][1] is None
+    assert res[0][2] and res[1][2], 'a frozen parameter had a gradient after a train() call'
+    start = _net().state_dict()
+    for k in ('0.weight', '2.bias'):
+        assert np.array_equal(res[0][0][k], start[k].numpy()), k
+    ref = _net().double()
+    ref[0].weight.requires_grad_(False)
+    ref[2].bias.requires_grad_(False)
+    opt = torch.optim.Adam(ref.parameters(), lr=0.05, weight_decay=0.01)
+    data = _batches(6)
+    for step in range(1, 5):
+        x, y = data[step - 1]
+        opt.zero_grad()
+        torch.nn.functional.mse_loss(ref(x.double()), y.double()).backward()
+        opt.step()
+    moved = 0.0
+    for k, v in ref.state_dict().items():
+        assert np.abs(v.numpy() - res[0][0][k]).max() <= 2e-6, k
+        moved = max(moved, float((v - start[k].double()).abs().max()))
+    assert moved > 0.1, 'four Adam steps of 0.05 move the trainable parameters'
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('toggle', ['freeze', 'unfreeze'])
+def test_reducer_refuses_a_changed_trainable_set(tmp_path, toggle):
+    res = _run_frozen(tmp_path, toggle)
+    for rank in (0, 1):
+        sd, err, none_ok = res[rank]
+        assert err is not None and err[0] == 3, 'the step after the toggle raises on rank %d' % rank
+        msg = err[1]
+        assert 'FlatGradReducer' in msg and 'build a new one' in msg
+        assert ('2 parameters' in msg and ('1 do now' if toggle == 'freeze' else '3 do now') in msg), msg
+    for k in res[0][0]:
+        assert np.array_equal(res[0][0][k], res[1][0][k]), k              # both stopped after the same two steps
