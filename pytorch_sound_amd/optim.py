@@ -198,3 +198,47 @@ class AdamW(Adam):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+
+
+def adopt(opt) -> bool:
+    """a stock `torch.optim.Adam` / `AdamW` that the kernel covers (the checks below) becomes this module's Adam / AdamW IN PLACE - the instance
+    keeps its identity, param_groups and state, its class changes - and True is returned; any other optimizer is left untouched: False"""
+    if type(opt) not in (torch.optim.Adam, torch.optim.AdamW):
+        return False
+    # an LR scheduler's constructor patches the INSTANCE's step() with a wrapper that notes `_opt_called` (torch's "scheduler before
+    # optimizer" warning).  The wrapper binds the class's step it saw, so it is taken off and an equivalent one put back after the class
+    # swap; any other instance-level patch is left alone
+    sched_wrapper = opt.__dict__.get('step')
+    if sched_wrapper is not None and not (getattr(sched_wrapper, '_wrapped_by_lr_sched', False)
+                                          and getattr(sched_wrapper, '__wrapped__', None) is type(opt).step):
+        return False
+    from torch.optim import optimizer as topt
+    if (getattr(opt, '_optimizer_step_pre_hooks', None) or getattr(opt, '_optimizer_step_post_hooks', None)
+            or getattr(topt, '_global_optimizer_pre_hooks', None) or getattr(topt, '_global_optimizer_post_hooks', None)):
+        return False                                  # step hooks are torch's step() protocol: keep torch's own step (and eager steps)
+    decoupled = set()
+    for g in opt.param_groups:
+        if (g.get('amsgrad') or g.get('maximize') or g.get('differentiable') or g.get('capturable')
+                or any(isinstance(g[k], torch.Tensor) for k in ('lr', 'eps', 'weight_decay')) or any(isinstance(b, torch.Tensor) for b in g['betas'])
+                or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in g['params'])):
+            return False
+        # torch >= 2.6: Adam(decoupled_weight_decay=True) is AdamW's update under Adam's type (and AdamW sets the key itself)
+        decoupled.add(g.get('decoupled_weight_decay', type(opt) is torch.optim.AdamW))
+    if not decoupled <= {True, False} or len(decoupled) != 1:
+        return False                                  # groups that disagree, or a value the kernel does not implement
+    opt.__dict__.pop('step', None)
+    opt.__class__ = AdamW if decoupled == {True} else Adam
+    opt._plans = {}
+    if sched_wrapper is not None:
+        import functools
+        import weakref
+        opt_ref, func = weakref.ref(opt), type(opt).step
+
+        @functools.wraps(func)
+        def wrapper(*args, **kwargs):
+            o = opt_ref()
+            o._opt_called = True
+            return func.__get__(o, o.__class__)(*args, **kwargs)
+        wrapper._wrapped_by_lr_sched = True
+        opt.step = wrapper
+    return True

@@ -14,6 +14,7 @@ lines.  What is new sits behind that surface:
 """
 import abc
 import contextlib
+import dataclasses
 import enum
 import glob
 import os
@@ -153,6 +154,73 @@ def dist_backend_is_nccl() -> bool:
     return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_backend() == 'nccl'
 
 
+@dataclasses.dataclass
+class CapturedStep:
+    """what Trainer._graphs keeps per batch signature"""
+    seen: int = 0                  # eager warm-up steps so far; everything below is set by the capture
+    graph: Any = None              # torch.cuda.CUDAGraph: gradient reset, forward(), the NaN flag, backward
+    inputs: Tuple = None           # the static tensors the graph reads its batch from
+    flag: torch.Tensor = None      # its NaN flag
+    grads: Dict = None             # parameter -> its static gradient in the graph's memory pool
+    ddp: str = None                # how the reducer takes part: 'events' / 'capture' / 'deferred'; None without a reducer
+
+    @property
+    def captured(self) -> bool:
+        return self.graph is not None
+
+    # bench.py reads these records the way a mapping is read: a field is `in` the record once it is set, and `.get(field)`
+    def __contains__(self, field: str) -> bool:
+        return getattr(self, field, None) is not None
+
+    def get(self, field: str, default=None):
+        return getattr(self, field, default)
+
+
+@dataclasses.dataclass
+class LookAheadState:
+    """Trainer._lr_state (see `async_scheduler`)"""
+    ring: torch.Tensor             # pinned (_LR_RING, groups) fp32: row j % _LR_RING = the rates of all groups after j successful steps
+    ring_np: np.ndarray            # its numpy view
+    count: torch.Tensor            # int32 on the device: the successful steps, counted by the optimizer launch
+    ahead: Any = None              # lr_ahead.LookAhead: the shadow scheduler that fills the ring
+    good: int = 0                  # successful steps confirmed on the host = steps the real scheduler has taken
+    filled: int = -1               # the last row written
+    seen: Any = None               # _lr_fingerprint() when the Trainer last left the scheduler
+    stale: bool = False            # a poll replayed scheduler steps on top of an edit by hand: rebuild before the next launch
+
+    def __getitem__(self, field: str):                 # callers written for the mapping this was: st['count'], st['ring']
+        return getattr(self, field)
+
+
+# A step's NaN flag on its way to the host, two kinds.  skipped(block): None while it has not arrived, then whether the step was skipped.
+class _RingFlag:
+    """the optimizer launch itself leaves {flag, seq} in row `slot` of the pinned ring (Trainer._nan_ring_buf)"""
+    counts_for_scheduler = True    # the launch that wrote it also chose the learning rate on the device: the real scheduler follows
+
+    def __init__(self, step, ring, slot, seq):
+        self.step, self.ring, self.slot, self.seq = step, ring, slot, seq
+
+    def skipped(self, block: bool):
+        arrived = int(self.ring[self.slot, 1]) == self.seq     # the sequence number is read first: the flag next to it is then this step's
+        return int(self.ring[self.slot, 0]) != 0 if arrived else None
+
+
+class _CopiedFlag:
+    """a pinned scalar, an asynchronous copy into it and an event behind the copy"""
+    counts_for_scheduler = False
+
+    def __init__(self, step, flag):
+        # the copy is enqueued BEHIND the optimizer launch (which reads the flag on the device): off the step's critical path
+        self.step, self.host_flag, self.event = step, torch.empty((), dtype=torch.float32, pin_memory=True), torch.cuda.Event()
+        self.host_flag.copy_(flag, non_blocking=True)
+        self.event.record()
+
+    def skipped(self, block: bool):
+        if block:
+            self.event.synchronize()
+        return float(self.host_flag.item()) > 0 if self.event.query() else None
+
+
 class Trainer:
 
     def __init__(self, model: nn.Module, optimizer: torch.optim.Optimizer,
@@ -190,6 +258,10 @@ class Trainer:
         os.makedirs(self.log_dir, exist_ok=True)
         self.writer = _make_writer(self.log_dir, pdist.is_main())
 
+        # the mutable step state (every other default is a class attribute next to the option it serves); load() reads it already
+        self._graphs = {}                             # batch signature -> CapturedStep, most recently used last
+        self._nan_pending = []                        # _RingFlag / _CopiedFlag of the steps whose flag has not reached the host, oldest first
+        self._reducer = None
         self.seed = None
         self.load()                                   # restores step / weights (and a seed, see below)
         # as in the reference (trainer.py:124-130) the constructor argument wins over a restored seed
@@ -217,7 +289,6 @@ class Trainer:
         self.save_valid_loss = np.finfo(np.float32).max
 
         # data parallel: identical start on every rank, overlapped gradient all-reduce
-        self._reducer = None
         force = os.environ.get('PSND_DDP_FORCE') == '1' and torch.distributed.is_available() and torch.distributed.is_initialized()
         if pdist.is_dist() or force:                   # force: a one-rank process group still runs the whole reducer path
             pdist.broadcast_module(self._bare_model)
@@ -238,52 +309,13 @@ class Trainer:
         self.__dict__['_step'] = v
 
     def _maybe_adopt_optimizer(self):
-        if self._opt_adopted is not None:
+        if self._opt_adopted is not None:              # looked at once
             return
         self._opt_adopted = False
-        opt = self.optimizer
-        if not self.adopt_optimizer or type(opt) not in (torch.optim.Adam, torch.optim.AdamW):
-            return
-        # an LR scheduler's constructor patches the INSTANCE's step() with a wrapper that notes `_opt_called` (torch's "scheduler before
-        # optimizer" warning).  The wrapper binds the class's step it saw, so it is taken off and an equivalent one put back after the class
-        # swap; any other instance-level patch is left alone
-        sched_wrapper = opt.__dict__.get('step')
-        if sched_wrapper is not None and not (getattr(sched_wrapper, '_wrapped_by_lr_sched', False)
-                                              and getattr(sched_wrapper, '__wrapped__', None) is type(opt).step):
-            return
-        from torch.optim import optimizer as topt
-        if (getattr(opt, '_optimizer_step_pre_hooks', None) or getattr(opt, '_optimizer_step_post_hooks', None)
-                or getattr(topt, '_global_optimizer_pre_hooks', None) or getattr(topt, '_global_optimizer_post_hooks', None)):
-            return                                    # step hooks are torch's step() protocol: keep torch's own step (and eager steps)
         from pytorch_sound_amd import optim as poptim
-        decoupled = set()
-        for g in opt.param_groups:
-            if (g.get('amsgrad') or g.get('maximize') or g.get('differentiable') or g.get('capturable')
-                    or any(isinstance(g[k], torch.Tensor) for k in ('lr', 'eps', 'weight_decay')) or any(isinstance(b, torch.Tensor) for b in g['betas'])
-                    or not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() for p in g['params'])):
-                return
-            # torch >= 2.6: Adam(decoupled_weight_decay=True) is AdamW's update under Adam's type (and AdamW sets the key itself)
-            decoupled.add(g.get('decoupled_weight_decay', type(opt) is torch.optim.AdamW))
-        if not decoupled <= {True, False} or len(decoupled) != 1:
-            return                                    # groups that disagree, or a value the kernel does not implement
-        if sched_wrapper is not None:
-            del opt.__dict__['step']
-        opt.__class__ = poptim.AdamW if decoupled == {True} else poptim.Adam
-        opt._plans = {}
-        if sched_wrapper is not None:
-            import functools
-            import weakref
-            opt_ref, func = weakref.ref(opt), type(opt).step
-
-            @functools.wraps(func)
-            def wrapper(*args, **kwargs):
-                o = opt_ref()
-                o._opt_called = True
-                return func.__get__(o, o.__class__)(*args, **kwargs)
-            wrapper._wrapped_by_lr_sched = True
-            opt.step = wrapper
-        self._opt_adopted = True
-        self._log('optimizer %s adopted: its steps run as one HIP launch (pytorch_sound_amd.optim)' % type(opt).__name__)
+        if self.adopt_optimizer and poptim.adopt(self.optimizer):
+            self._opt_adopted = True
+            self._log('optimizer %s adopted: its steps run as one HIP launch (pytorch_sound_amd.optim)' % type(self.optimizer).__name__)
 
     # ------------------------------------------------------------------------------------------
     @property
@@ -303,8 +335,7 @@ class Trainer:
 
     def _watch_host_state(self) -> bool:
         """graph_steps = 'auto' and a step could still be captured: an eager forward() is watched for host-side decisions"""
-        return (self.graph_steps == 'auto' and self._graph_auto_ok is not False and getattr(self, '_reducer', None) is None
-                and self.async_nan_check and self._scheduler_rides_along() and getattr(self.optimizer, '_step_supports_amp_scaling', False)
+        return (self.graph_steps == 'auto' and self._graph_auto_ok is not False and self._reducer is None and self._device_skip_open()
                 and torch.cuda.is_available() and not torch.cuda.is_current_stream_capturing())
 
     def _forward_resolved(self, *inputs, is_logging: bool = False, watch: bool = False):
@@ -367,29 +398,33 @@ class Trainer:
             if changed:
                 self._log('the model changed (requires_grad / train-eval flags): captured steps are dropped and captured again')
 
+    def _drop_graphs(self) -> bool:
+        # forget every captured step and warm-up count; True when a captured step was among them
+        had = any(v.captured for v in self._graphs.values())
+        if had:
+            torch.cuda.synchronize()                     # no replay of them still in flight
+        self._graphs = {}
+        return had
+
     def reset_graphs(self):
         """forget every captured step and its warm-up count (after a synchronize), set `.grad = None` on every parameter that does not
         require a gradient, look at the optimizer's coverage again; the next steps run eagerly, warm up and are captured as at the start.
         Called by train() when model_fingerprint() changed; call it yourself after an edit the fingerprint cannot see."""
-        if any('graph' in v for v in getattr(self, '_graphs', {}).values()):
-            torch.cuda.synchronize()                     # no replay of them still in flight
-        self._graphs = {}
+        self._drop_graphs()
         params, modules = self._model_lists(refresh=True)
         self._model_fp = model_fingerprint(params, modules)
         for p in params:
             if not p.requires_grad:
                 p.grad = None                            # (a dropped graph's static gradient, a bucket view, a backward from before the freeze)
         self._opt_cover = None
-        if getattr(self, '_reducer', None) is not None:
+        if self._reducer is not None:
             self._reducer.check_trainable()              # raises: its buckets were laid out for another trainable set
 
     def _stay_eager(self, why: str):
         """graph_steps = 'auto' after a forward() that made a host-side decision: no capture from now on, and graphs captured before it (the
         decision showed on a logging step or on the warm-up of another input signature) are dropped"""
-        if any('graph' in v for v in getattr(self, '_graphs', {}).values()):
-            torch.cuda.synchronize()                     # no replay of them still in flight
+        if self._drop_graphs():
             why += ' (after a capture: the captured steps are dropped)'
-        self._graphs = {}
         self._graph_auto_ok = False
         self._log("graph_steps = 'auto': %s - the steps stay eager (set graph_steps = True to capture anyway)" % why)
 
@@ -429,45 +464,20 @@ class Trainer:
         if self.prefetch_copy:
             self._log('batches arrive in pinned host memory: the next batch is copied on a side stream while a step computes '
                       '(Trainer.prefetch_copy; set it to False for the in-line copy)')
-        batch = to_device(raw) if gpu else items
-        return self.prepare(*batch)
+        return self.prepare(*(to_device(raw) if gpu else items))
 
-    # (not in the reference) prepare() of batch k+1 on a side stream BEHIND step k's forward / backward: the side stream waits for
-    # the step's last backward kernel (so persistent feature buffers - static_prepare - are free again) and its feature extraction runs
-    # next to step k's optimizer launch and step k+1's weight prep, which leave most of the chip idle; step k+1 waits on an event.
-    # prepare() must be parameter-free.  The data iterator is advanced one batch ahead of the step that uses it.
-    overlap_prepare = False
+    _pre_stream = None             # the side stream of either mode (_independent_stream(), probed at first use or by setup_prefetch())
+    _pre = None                    # what it staged last: (batch, event), or (StopIteration, None) at the end of the data
 
-    def _stage_overlapped(self):
-        """called right behind the step's backward (graph replay) on the compute stream"""
-        if not (self.overlap_prepare and torch.cuda.is_available()) or self.prefetch_prepare or self.prefetch_copy:
-            return
-        if getattr(self, '_ovl_stream', None) is None:
-            self._ovl_stream = _independent_stream()
-        side, cur = self._ovl_stream, torch.cuda.current_stream()
-        side.wait_stream(cur)
+    def _stage_next_batch(self):
+        # the next batch's copy (and, under prefetch_prepare, its prepare()) enqueued on the side stream, an event behind it
         try:
-            with torch.cuda.stream(side):
-                raw = tuple(self._next_batch(self.train_dataset))
-                for t in raw:
-                    if isinstance(t, torch.Tensor) and t.is_cuda:
-                        t.record_stream(side)
-                batch = self.prepare(*raw)
-                event = torch.cuda.Event()
-                event.record(side)
-            self._ovl = (batch, event)
-        except StopIteration as e:                       # surfaces at the step that would have used the batch
-            self._ovl = (e, None)
-
-    def _stage_train_batch(self):
-        side = self._pre_stream
-        try:
-            with torch.cuda.stream(side):
+            with torch.cuda.stream(self._pre_stream):
                 batch = tuple(self._next_batch(self.train_dataset))
                 if self.prefetch_prepare:
                     batch = self.prepare(*batch)
                 event = torch.cuda.Event()
-                event.record(side)
+                event.record(self._pre_stream)
             return batch, event
         except StopIteration as e:                       # surfaces at the step that would have used the batch
             return e, None
@@ -475,48 +485,38 @@ class Trainer:
     def setup_prefetch(self):
         """probe for the side stream now (a 64 MB scratch buffer, ~20 ms) instead of inside the first training step - call it
         before the model's memory peaks when the GPU is nearly full"""
-        if (self.prefetch_prepare or self.prefetch_copy) and torch.cuda.is_available() and getattr(self, '_pre_stream', None) is None:
+        if (self.prefetch_prepare or self.prefetch_copy) and torch.cuda.is_available() and self._pre_stream is None:
             self._pre_stream = _independent_stream()
 
+    @staticmethod
+    def _take_staged_batch(batch, event):
+        # a staged batch handed to the current stream: it waits for the event (the host does not), the allocator learns of the new user
+        if event is None:
+            raise batch                                  # the StopIteration, at the step that would have used the batch
+        cur = torch.cuda.current_stream()
+        cur.wait_event(event)
+        for t in batch:
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                t.record_stream(cur)
+        return batch
+
     def _take_train_batch(self):
-        if self.prefetch_copy is None and getattr(self, '_ovl', None) is None:
+        if self.prefetch_copy is None:
             return self._decide_prefetch_copy()
         if not ((self.prefetch_prepare or self.prefetch_copy) and torch.cuda.is_available()):
-            ovl = getattr(self, '_ovl', None)
-            if ovl is not None:                          # staged behind the previous step (overlap_prepare)
-                self._ovl = None
-                batch, event = ovl
-                if event is None:
-                    raise batch
-                cur = torch.cuda.current_stream()
-                cur.wait_event(event)
-                for t in batch:
-                    if isinstance(t, torch.Tensor) and t.is_cuda:
-                        t.record_stream(cur)
-                return batch
-            return self.prepare(*self._next_batch(self.train_dataset))
+            return self.prepare(*self._next_batch(self.train_dataset))      # in line, as the reference does
         if self.prefetch_prepare and self.static_prepare:
             # prepare() of batch k+1 runs on the side stream BEFORE step k's graph replay is enqueued: with persistent feature
             # buffers (static_prepare) it would overwrite the very tensors that replay is about to read
             raise ValueError('Trainer.prefetch_prepare and Trainer.static_prepare are mutually exclusive: a prepare() that runs '
                              'one step ahead must return fresh tensors (set static_prepare = False), or only the copy may run '
                              'ahead (prefetch_copy)')
-        if getattr(self, '_pre_stream', None) is None:
-            self._pre_stream = _independent_stream()
-        if getattr(self, '_pre', None) is None:
-            self._pre = self._stage_train_batch()
-        batch, event = self._pre
-        if event is None:
-            raise batch
-        self._pre = self._stage_train_batch()            # enqueued ahead of this step's own kernels: overlaps with them
-        cur = torch.cuda.current_stream()
-        cur.wait_event(event)
-        for t in batch:
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.record_stream(cur)
-        if not self.prefetch_prepare:
-            batch = self.prepare(*batch)
-        return batch
+        self.setup_prefetch()
+        staged = self._pre or self._stage_next_batch()
+        # the batch after it is enqueued ahead of this step's own kernels: overlaps with them (the end of the data stays where it is)
+        self._pre = self._stage_next_batch() if staged[1] is not None else staged
+        batch = self._take_staged_batch(*staged)
+        return batch if self.prefetch_prepare else self.prepare(*batch)
 
     # (not in the reference) False keeps the batches where the data set put them - a CPU training run on a machine that has a GPU
     # (the reference moves every batch with .cuda() unconditionally, trainer.py:202)
@@ -566,9 +566,15 @@ class Trainer:
     # host on its own.  Anything else falls back to the reference's synchronous check.
     async_nan_check = True
 
+    def _device_skip_open(self) -> bool:
+        """the device-skip path is open: no host check needed (switch, scheduler, optimizer; the callers add what they know of the tensors)"""
+        return self.async_nan_check and self._scheduler_rides_along() and getattr(self.optimizer, '_step_supports_amp_scaling', False)
+
     def _can_skip_on_device(self, loss: torch.Tensor) -> bool:
-        return (self.async_nan_check and loss.is_cuda and self._scheduler_rides_along()
-                and getattr(self.optimizer, '_step_supports_amp_scaling', False))
+        return loss.is_cuda and self._device_skip_open()
+
+    def _log_nan(self, step: int):
+        self._log('{} cur step NAN is occured'.format(step))
 
     # ---- LR schedulers on the device-skip path ---------------------------------------------------------------
     # The reference steps its scheduler after every SUCCESSFUL step (trainer.py:211-214): a skipped step does not advance the schedule, and
@@ -586,10 +592,11 @@ class Trainer:
     # absolute value (`lr = 1e-4`) is then decayed further by StepLR / ExponentialLR, and overwritten by a closed-form one, than the
     # synchronous loop would have.
     # False, a scheduler that is not eligible (ReduceLROnPlateau, momentum cycling, foreign objects), CPU tensors or an optimizer without
-    # the `lr_ahead` protocol: the reference's synchronous check, as before.
+    # the `lr_ahead` protocol: the reference's synchronous check.
     async_scheduler = True
     _LR_RING = 256
-    _lr_state = None
+    _lr_state = None               # LookAheadState; None: nothing staged (rebuilt from the scheduler's state at the next step)
+    _lr_eligible = None            # (scheduler, whether it rides along): looked at, and logged, once per scheduler object
 
     def _scheduler_rides_along(self) -> bool:
         """no scheduler, or one whose steps can be chosen on the device"""
@@ -598,7 +605,7 @@ class Trainer:
         if not (self.async_scheduler and getattr(self.optimizer, '_supports_lr_ahead', False)
                 and getattr(self.optimizer, '_supports_flag_log', False)):
             return False
-        known = getattr(self, '_lr_eligible', None)
+        known = self._lr_eligible
         if known is None or known[0] is not self.scheduler:
             from pytorch_sound_amd import lr_ahead
             why = lr_ahead.why_not_eligible(self.scheduler)
@@ -618,13 +625,12 @@ class Trainer:
         from pytorch_sound_amd import lr_ahead
         st = self._lr_state
         ahead = lr_ahead.LookAhead(self.scheduler, keep=self._LR_RING)
-        if st is None or st['ring'].shape != (self._LR_RING, ahead.n_groups) or st['count'].device != device:
-            st = self._lr_state = {'ring': torch.zeros((self._LR_RING, ahead.n_groups), dtype=torch.float32).pin_memory(),
-                                   'count': torch.zeros((), dtype=torch.int32, device=device)}
-            st['ring_np'] = st['ring'].numpy()
+        if st is None or st.ring.shape != (self._LR_RING, ahead.n_groups) or st.count.device != device:
+            ring = torch.zeros((self._LR_RING, ahead.n_groups), dtype=torch.float32).pin_memory()
+            st = self._lr_state = LookAheadState(ring, ring.numpy(), torch.zeros((), dtype=torch.int32, device=device))
         else:
-            st['count'].zero_()
-        st.update(ahead=ahead, good=0, filled=-1, seen=self._lr_fingerprint(), stale=False)
+            st.count.zero_()
+        st.ahead, st.good, st.filled, st.seen, st.stale = ahead, 0, -1, self._lr_fingerprint(), False
         return st
 
     def _lr_stage(self, device):
@@ -635,14 +641,12 @@ class Trainer:
             self._poll_nan_log(block=True)             # the shadow is a whole ring ahead of the confirmed steps: let the host catch up
         # edited by hand / stepped by the caller (seen here, or by a poll that replayed scheduler steps on top of the edit: `stale`):
         # catch up, then start from what is there now
-        if st is not None and (st['stale'] or st['seen'] != self._lr_fingerprint() or st['ring'].shape[0] != rows):
-            st = None
-        if st is None:
+        if st is None or st.stale or st.seen != self._lr_fingerprint() or st.ring.shape[0] != rows:
             self._poll_nan_log(block=True)
             st = self._lr_rebuild(device)
-        top = st['good'] + len(self._nan_pending)      # this step's count of successes before it: st['good'] .. top
+        top = st.good + len(self._nan_pending)         # this step's count of successes before it: st.good .. top
         try:
-            fresh = [(j, st['ahead'].row(j)) for j in range(st['filled'] + 1, top + 1)]
+            fresh = [(j, st.ahead.row(j)) for j in range(st.filled + 1, top + 1)]
         except ValueError:
             # a schedule that ends (OneCycleLR's total_steps: "Tried to step N times"): `top` counts the steps in flight as successes, skipped
             # ones included, and may lie past an end the run itself never reaches.  The shadow has half-taken that step: catch up and begin
@@ -653,28 +657,28 @@ class Trainer:
                 raise
             self._poll_nan_log(block=True)
             st = self._lr_rebuild(device)
-            fresh = [(0, st['ahead'].row(0))]
+            fresh = [(0, st.ahead.row(0))]
         for j, row in fresh:
             if not all(v >= 0.0 for v in row):         # (NaN fails too) what psnd_adam_step refuses as an argument must not reach the ring
                 raise ValueError('the scheduler yields the learning rates %r after %d more successful steps: '
                                  'the optimizer takes finite rates >= 0' % (row, j))
-            st['ring_np'][j % rows] = row              # (fp32 image of the double, rounded as the kernel argument of psnd_adam_step is)
-            st['filled'] = j
-        return (st['ring'], rows, st['count'])
+            st.ring_np[j % rows] = row                 # (fp32 image of the double, rounded as the kernel argument of psnd_adam_step is)
+            st.filled = j
+        return (st.ring, rows, st.count)
 
     def _lr_confirmed(self, skipped: bool):
         """a step's flag has reached the host (in order): the real scheduler takes the step the device already took"""
         st = self._lr_state
         if skipped or st is None:
             return
-        if st['seen'] != self._lr_fingerprint():
+        if st.seen != self._lr_fingerprint():
             # a rate written by hand (or a scheduler stepped by the caller) since the Trainer last looked: the step is replayed on top of
             # it, as the synchronous loop would have, but `seen` keeps the difference - _lr_stage rebuilds the shadow before the next launch
-            st['stale'] = True
+            st.stale = True
         self.scheduler.step()
-        st['good'] += 1
-        if not st['stale']:
-            st['seen'] = self._lr_fingerprint()
+        st.good += 1
+        if not st.stale:
+            st.seen = self._lr_fingerprint()
 
     def sync_scheduler(self):
         """wait for the steps in flight and replay their scheduler steps: `scheduler` and `param_groups[i]['lr']` are then exactly where
@@ -687,44 +691,25 @@ class Trainer:
     # optimizer launch were ~14 us of a 0.67 ms config-2 step.  Other optimizers: a pinned scalar, an asynchronous copy and an event.
     _NAN_RING = 256
 
-    def _nan_ring(self):
-        ring = getattr(self, '_nan_ring_buf', None)
-        if ring is None:
-            ring = self._nan_ring_buf = torch.zeros((self._NAN_RING, 2), dtype=torch.int32).pin_memory()
-            self._nan_seq = 0
-        return ring
+    _nan_ring_buf = None           # that ring: pinned (_NAN_RING, 2) int32, made at the first step that uses it
+    _nan_seq = 0                   # the sequence number of the slot handed out last
 
     def _poll_nan_log(self, block: bool = False):
-        pending = getattr(self, '_nan_pending', None)
-        if not pending:
+        if not self._nan_pending:
             return
         if block and torch.cuda.is_available():
             torch.cuda.synchronize()
         keep = []
-        in_order = self._lr_state is not None          # scheduler steps are replayed in the order of the training steps
-        for entry in pending:
-            step, host_flag, event = entry
-            if in_order and keep:
+        in_order = self._lr_state is not None          # scheduler steps are replayed in the order of the training steps:
+        for entry in self._nan_pending:                # once an entry is kept, every later one is kept
+            skipped = None if in_order and keep else entry.skipped(block)
+            if skipped is None:
                 keep.append(entry)
                 continue
-            if isinstance(event, int):                 # ring slot: host_flag = the slot, event = the sequence number to wait for
-                ring = self._nan_ring_buf
-                if int(ring[host_flag, 1]) == event:
-                    skipped = int(ring[host_flag, 0]) != 0
-                    if skipped:
-                        self._log('{} cur step NAN is occured'.format(step))
-                    if in_order:
-                        self._lr_confirmed(skipped)
-                else:
-                    keep.append(entry)
-                continue
-            if block:
-                event.synchronize()
-            if event.query():
-                if float(host_flag.item()) > 0:
-                    self._log('{} cur step NAN is occured'.format(step))
-            else:
-                keep.append(entry)
+            if skipped:
+                self._log_nan(entry.step)
+            if in_order and entry.counts_for_scheduler:
+                self._lr_confirmed(skipped)
         self._nan_pending = keep
 
     @staticmethod
@@ -743,19 +728,26 @@ class Trainer:
             return flag
         return torch.isnan(x).any().to(torch.float32).reshape(())
 
+    _root_grad = None              # the fp32 one that every backward starts from (per device)
+
+    def _root_gradient(self, device) -> torch.Tensor:
+        if self._root_grad is None or self._root_grad.device != device:
+            self._root_grad = torch.ones((), dtype=torch.float32, device=device)
+        return self._root_grad
+
     def _backward(self, loss: torch.Tensor):
         """loss.backward() with a persistent root gradient (autograd's own ones_like is a fill launch per step)"""
         if loss.dim() == 0 and loss.is_cuda and loss.dtype == torch.float32:
-            one = getattr(self, '_root_grad', None)
-            if one is None or one.device != loss.device:
-                one = self._root_grad = torch.ones((), dtype=torch.float32, device=loss.device)
-            loss.backward(gradient=one)
+            loss.backward(gradient=self._root_gradient(loss.device))
         else:
             loss.backward()
 
+    def _reducer_takes_part(self) -> bool:             # in this step (`active` without is_dist(): a forced one-rank group)
+        return self._reducer is not None and (pdist.is_dist() or self._reducer.active)
+
     def _train_device_skip(self, step: int, loss: torch.Tensor):
         flag = self._nan_flag(loss)
-        if self._reducer is not None and (pdist.is_dist() or self._reducer.active):   # (the same condition as _finish_device_skip: a forced one-rank group)
+        if self._reducer_takes_part():
             self._reducer.set_flag(flag)               # rides along with the last gradient bucket
         self._backward(loss)
         self._finish_device_skip(step, flag)
@@ -778,7 +770,7 @@ class Trainer:
     # CUDA inputs, no scheduler or one whose rate is chosen on the device (async_scheduler), an optimizer with the found_inf protocol (fused Adam/AdamW/SGD), a forward()
     # free of host synchronisation.  Logging steps and the first `graph_warmup` steps of a signature run eagerly.
     #
-    # graph_steps = 'auto' (default, round 6): capture when it is SAFE to - no gradient reducer (a data-parallel run opts in with True, all
+    # graph_steps = 'auto' (default): capture when it is SAFE to - no gradient reducer (a data-parallel run opts in with True, all
     # ranks alike), and during the eager warm-up steps forward() neither consumed host-side randomness (python `random`, numpy's global
     # RandomState - its whole state, gauss cache included -, torch's default CPU generator, any torch.Generator handed to a torch function)
     # nor read `self.step`: a replayed step repeats the HOST-side decisions of the captured call, so a forward that draws a crop on the host
@@ -791,6 +783,9 @@ class Trainer:
     graph_steps = 'auto'
     graph_warmup = 3
     _graph_auto_ok = None          # 'auto': None undecided / True / False (stay eager)
+    _auto_caps = 0                 # 'auto': signatures captured so far ...
+    _auto_replays = 0              # ... and steps replayed (any mode), see _train_graph
+    _ddp_time_marks = False        # lab: FlatGradReducer.after_replay(time_marks=) records a timing event where every bucket is released
     # Trainer adopts a stock `torch.optim.Adam` / `AdamW` handed to it (exact types, amsgrad / maximize / capturable off, fp32 HIP
     # parameters, no step hooks of its own or global ones): the instance keeps its identity, param_groups and state, its class becomes
     # pytorch_sound_amd.optim.Adam / AdamW (AdamW also for an Adam with decoupled_weight_decay=True) - one launch per step, on-device NaN
@@ -802,38 +797,31 @@ class Trainer:
     static_prepare = False
 
     def _train_graph(self, step: int, batch) -> bool:
-        if not (self.async_nan_check and self._scheduler_rides_along()
-                and getattr(self.optimizer, '_step_supports_amp_scaling', False)
-                and all(isinstance(t, torch.Tensor) and t.is_cuda for t in batch)):
+        if not (self._device_skip_open() and all(isinstance(t, torch.Tensor) and t.is_cuda for t in batch)):
             return False
-        if not hasattr(self, '_graphs'):
-            self._graphs = {}
         sig = tuple((tuple(t.shape), t.dtype) for t in batch)
-        st = self._graphs.pop(sig, None) or {'seen': 0}
+        st = self._graphs.pop(sig, None) or CapturedStep()
         self._graphs[sig] = st                         # most recently used last
-        if 'graph' not in st:
-            if st['seen'] < self.graph_warmup:
-                st['seen'] += 1
+        if not st.captured:
+            if st.seen < self.graph_warmup:
+                st.seen += 1
                 self._trim_graph_cache()
                 return False
             if self.graph_steps == 'auto':
                 # variable-length batches (a bucketed loader) bring a new input signature every few steps: a capture costs ~0.1 s and pays only
                 # when its signature comes back - once 8 signatures are captured and each was replayed fewer than 8 times on average, new
                 # signatures run eagerly (the captured ones keep replaying)
-                caps, reps = getattr(self, '_auto_caps', 0), getattr(self, '_auto_replays', 0)
-                if caps >= 8 and reps < 8 * caps:
+                if self._auto_caps >= 8 and self._auto_replays < 8 * self._auto_caps:
                     return False
                 try:
                     self._capture(st, batch)
                     self._graph_auto_ok = True
-                    self._auto_caps = caps + 1
+                    self._auto_caps += 1
                 except Exception as e:                 # noqa: BLE001 - a forward() that cannot be captured: stay eager, say why once
                     self._graph_auto_ok = False
                     self._graphs.pop(sig, None)
-                    try:
+                    with contextlib.suppress(Exception):
                         torch.cuda.synchronize()
-                    except Exception:                  # noqa: BLE001
-                        pass
                     for p in self._bare_model.parameters():
                         p.grad = None
                     self._log("graph_steps = 'auto': the step could not be captured (%s) - the steps stay eager" % repr(e)[:200])
@@ -841,24 +829,23 @@ class Trainer:
             else:
                 self._capture(st, batch)
             self._trim_graph_cache()
-        for dst, src in zip(st['inputs'], batch):
+        for dst, src in zip(st.inputs, batch):
             if src.data_ptr() != dst.data_ptr():           # static_prepare: already there
                 dst.copy_(src, non_blocking=True)
-        st['graph'].replay()
-        self._auto_replays = getattr(self, '_auto_replays', 0) + 1
-        self._stage_overlapped()                       # the next batch's prepare(): side stream, next to this step's optimizer launch
-        if self._reducer is not None and st.get('ddp') in ('events', 'capture'):
+        st.graph.replay()
+        self._auto_replays += 1
+        if self._reducer is not None and st.ddp in ('events', 'capture'):
             # the captured backward filled the flat buckets itself and marked where each is complete: bucket i is all-reduced
             # while the replay is still producing bucket i + 1 (FlatGradReducer, graph mode)
-            self._reducer.after_replay(st['ddp'], time_marks=getattr(self, '_ddp_time_marks', False))
+            self._reducer.after_replay(st.ddp, time_marks=self._ddp_time_marks)
         elif self._reducer is not None:                # deferred: into the flat buckets, reduced in _finish_device_skip
-            self._reducer.load_grads(st['grads'])
+            self._reducer.load_grads(st.grads)
             if self._reducer.active:
-                self._reducer.set_flag(st['flag'])
+                self._reducer.set_flag(st.flag)
         else:
-            for p, g in st['grads'].items():
+            for p, g in st.grads.items():
                 p.grad = g
-        self._finish_device_skip(step, st['flag'])
+        self._finish_device_skip(step, st.flag)
         return True
 
     # every captured signature owns a memory pool with that shape's activations: variable-length batches (bucketed loaders)
@@ -866,170 +853,178 @@ class Trainer:
     graph_cache_size = 8
 
     def _trim_graph_cache(self):
-        captured = [k for k, v in self._graphs.items() if 'graph' in v]
+        captured = [k for k, v in self._graphs.items() if v.captured]
         for k in captured[:max(0, len(captured) - self.graph_cache_size)]:
             del self._graphs[k]
         if len(self._graphs) > 64 * max(1, self.graph_cache_size):
-            for k in [k for k, v in self._graphs.items() if 'graph' not in v][:len(self._graphs) // 2]:
+            for k in [k for k, v in self._graphs.items() if not v.captured][:len(self._graphs) // 2]:
                 del self._graphs[k]
 
-    def _capture(self, st, batch):
+    # see cl.py: no extra graph branches (batch sections, resblock / parameter-side branches) next to other live streams; decided per
+    # capture - a Trainer without such streams captured later in the same process gets its branches back
+    def _graph_branches(self) -> bool:                 # cl.AUTO_SECTIONS for the capture at hand
         red = self._reducer
-        mode = red.graph_mode() if red is not None and red.active else None
-        # static_prepare: prepare() returns the SAME buffers every step (features written in place) - they are the graph's inputs
-        st['inputs'] = tuple(batch) if self.static_prepare else tuple(t.clone() for t in batch)
-        from . import cl
-        # see cl.py: no extra graph branches (batch sections, resblock / parameter-side branches) next to other live streams; decided per
-        # capture - a Trainer without such streams captured later in the same process gets its branches back
-        # Round 5: graph branches and a gradient reducer in one captured step.  The reducer releases every bucket from a stream of its own
+        # Graph branches and a gradient reducer share a captured step: the reducer releases every bucket from a stream of its own
         # behind the events of all streams that produced its gradients (distributed.FlatGradReducer._release_on: a captured RCCL all-reduce
         # issued from a graph branch ended the process in hipStreamEndCapture), and a parameter handed over from inside a node arrives once
         # (the engine calls the post-accumulate hooks of its AccumulateGrad node although the node returned None for it; counted twice,
-        # buckets left before their last gradients - zeros next to branches, an all-reduce ahead of its data on several ranks).
-        # PSND_DDP_BRANCHES=0: round 4's behaviour (no branches next to a reducer) for A/B runs.
+        # buckets are left before their last gradients - zeros next to branches, an all-reduce ahead of its data on several ranks).
+        # PSND_DDP_BRANCHES=0: no branches next to a reducer, for A/B runs.
         red_blocks = red is not None and red.active and _sw.lab('PSND_DDP_BRANCHES', '1') != '1'
-        # Round 5: next to `prefetch_copy` (a COPY-only side stream, picked by _independent_stream so that it runs next to the compute
+        # Next to `prefetch_copy` (a COPY-only side stream, picked by _independent_stream so that it runs next to the compute
         # stream) the branches stay on: config 3 with pinned host batches 2.86-2.93 ms with them, 3.55-3.65 without, 2.91 with the pool
         # on the device - six fresh processes each for configs 3 and 4, no slow step among them (tools/r05/prefetch_branches.py;
         # PSND_PREFETCH_BRANCHES=0 switches them off).  `prefetch_prepare` runs KERNELS on its side stream (prepare() of the next batch):
-        # that stream competes with the branches for the hardware queues, as measured in round 3 with batch sections - branches off.
-        pre_copy_only = (bool(self.prefetch_copy) or getattr(self, '_pre_stream', None) is not None) and not bool(self.prefetch_prepare)
+        # that stream competes with the branches for the hardware queues, as measured with batch sections - branches off.
+        pre_copy_only = (bool(self.prefetch_copy) or self._pre_stream is not None) and not bool(self.prefetch_prepare)
         pre_blocks = bool(self.prefetch_prepare) or (pre_copy_only and _sw.lab('PSND_PREFETCH_BRANCHES', '1') != '1')
-        cl.AUTO_SECTIONS = not (red_blocks or pre_blocks)
-        params = [p for p in self._bare_model.parameters() if p.requires_grad]
-        if getattr(self, '_root_grad', None) is None or self._root_grad.device != st['inputs'][0].device:
-            self._root_grad = torch.ones((), dtype=torch.float32, device=st['inputs'][0].device)   # not inside the capture
-        while True:
-            for p in params:
-                p.grad = None                          # backward then WRITES its gradients (no zero fill, no += kernels)
+        return not (red_blocks or pre_blocks)
+
+    def _capture_once(self, st: CapturedStep, params, mode):
+        """one attempt: the graph, or None when a capture with the all-reduces inside it ('events' / 'capture') failed on this rank"""
+        red = self._reducer
+        for p in params:
+            p.grad = None                              # backward then WRITES its gradients (no zero fill, no += kernels)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        try:
+            # thread_local: the process group's watchdog thread keeps querying events of earlier collectives while this
+            # thread captures ("operation not permitted when stream is capturing" under the default global mode)
+            with torch.cuda.graph(graph, capture_error_mode='thread_local' if red is not None else 'global'):
+                loss, _ = self._forward_resolved(*st.inputs, is_logging=False)
+                st.flag = self._nan_flag(loss)
+                if mode in ('events', 'capture'):
+                    red.capture_begin(st.flag, mode)   # the captured backward fills and releases the buckets itself
+                elif red is not None:
+                    red.deferred = True                # no collective from inside the captured backward
+                self._backward(loss)
+                if mode in ('events', 'capture'):
+                    red.capture_end()
+        except Exception as e:                         # noqa: BLE001 - e.g. a runtime that cannot capture the release nodes
+            if mode in (None, 'deferred'):
+                raise
+            self._log('graph capture with DDP mode %s failed (%s)' % (mode, repr(e)[:200]))
+            red._capturing = None
             torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            ok = True
-            try:
-                # thread_local: the process group's watchdog thread keeps querying events of earlier collectives while this
-                # thread captures ("operation not permitted when stream is capturing" under the default global mode)
-                with torch.cuda.graph(graph, capture_error_mode='thread_local' if red is not None else 'global'):
-                    loss, _ = self._forward_resolved(*st['inputs'], is_logging=False)
-                    st['flag'] = self._nan_flag(loss)
-                    if mode in ('events', 'capture'):
-                        red.capture_begin(st['flag'], mode)   # the captured backward fills and releases the buckets itself
-                    elif red is not None:
-                        red.deferred = True            # no collective from inside the captured backward
-                    self._backward(loss)
-                    if mode in ('events', 'capture'):
-                        red.capture_end()
-            except Exception as e:                     # noqa: BLE001 - e.g. a runtime that cannot capture the release nodes
-                if mode in (None, 'deferred'):
-                    raise
-                ok = False
-                self._log('graph capture with DDP mode %s failed (%s)' % (mode, repr(e)[:200]))
-                red._capturing = None
-                torch.cuda.synchronize()
-            finally:
-                if red is not None:
-                    red.deferred = False               # eager (logging) steps keep the overlapped per-bucket all-reduce
+            return None
+        finally:
+            if red is not None:
+                red.deferred = False                   # eager (logging) steps keep the overlapped per-bucket all-reduce
+        return graph
+
+    def _capture(self, st: CapturedStep, batch):
+        red = self._reducer
+        mode = red.graph_mode() if red is not None and red.active else None
+        # static_prepare: prepare() returns the SAME buffers every step (features written in place) - they are the graph's inputs
+        st.inputs = tuple(batch) if self.static_prepare else tuple(t.clone() for t in batch)
+        from . import cl
+        cl.AUTO_SECTIONS = self._graph_branches()
+        params = [p for p in self._bare_model.parameters() if p.requires_grad]
+        self._root_gradient(st.inputs[0].device)       # made here: not inside the capture
+        while True:
+            graph = self._capture_once(st, params, mode)
+            ok = graph is not None
             if mode in ('events', 'capture') and pdist.is_dist():
                 # every rank must replay the SAME collective sequence: a rank that fell back on its own would issue its all-reduces
                 # after the replay while the others have them inside the graph - agree (MIN over ranks) and fall back together
-                dev = st['flag'].device if dist_backend_is_nccl() else None
+                dev = st.flag.device if dist_backend_is_nccl() else None
                 ok = pdist.all_reduce_scalar(1.0 if ok else 0.0, 'min', dev) > 0
             if ok:
                 break
             self._log('falling back to the deferred all-reduce on every rank')
             del graph
             mode = 'deferred'
-        st['graph'] = graph
-        st['ddp'] = mode
-        st['grads'] = {p: p.grad for p in params}      # static tensors of the graph's memory pool
+        st.graph, st.ddp = graph, mode
+        st.grads = {p: p.grad for p in params}         # static tensors of the graph's memory pool
         self._log('captured the training step as a hipGraph for inputs %s' % (
             ', '.join('x'.join(map(str, t.shape)) for t in batch)))
+
+    _opt_cover = None              # ((the optimizer's id, its parameter count), the answer below); reset_graphs() looks again
 
     def _optimizer_covers_model(self) -> bool:
         """the fused clip takes its global norm over the OPTIMIZER's parameters; Trainer.clip_grad (trainer.py:184-191) over every model
         parameter that requires a gradient.  The two agree only when the sets agree - otherwise the stock clip_grad() runs.
         (With the fused clip `p.grad` itself stays unclipped - and un-averaged under DDP; read `optimizer.last_grad_norm`.)"""
         key = (id(self.optimizer), sum(len(g['params']) for g in self.optimizer.param_groups))
-        cached = getattr(self, '_opt_cover', None)
+        cached = self._opt_cover
         if cached is None or cached[0] != key:
             model = {id(p) for p in self._bare_model.parameters() if p.requires_grad}
             opt = {id(p) for g in self.optimizer.param_groups for p in g['params']}
             cached = self._opt_cover = (key, model == opt)
         return cached[1]
 
+    _world_scale = None            # the world size as a device scalar: the optimizer kernel's grad_scale when it averages over the ranks
+
+    def _finish_reduce(self, flag: torch.Tensor, fused_clip: bool):
+        # the reducer's part of the tail: the last collectives; returns the flag the optimizer skips on and its grad_scale
+        if not self._reducer_takes_part():
+            if self._reducer is not None:
+                self._reducer.finish()
+            return flag, None
+        # ONE collective per bucket: the flag sits behind the last bucket (set_flag), and when nothing clips the gradients the
+        # division by the world size is left to the optimizer kernel (grad_scale) instead of a pass over the buckets
+        in_opt = fused_clip or not (self.grad_clip or self.grad_norm)
+        self._reducer.finish(average=not in_opt)
+        # the sum of the ranks' 0 / 1 flags (divided by the world size when the buckets are averaged): psnd_adam_step skips on any
+        # non-zero value and takes it as it is; torch's fused optimizers test `found_inf == 1`, so they get it normalised (two launches)
+        rf = self._reducer.flag
+        raw_ok = rf.dtype == torch.float32 and getattr(self.optimizer, '_supports_flag_log', False)
+        flag = rf.reshape(()) if raw_ok else (rf > 0).to(torch.float32).reshape(())
+        if in_opt and (self._world_scale is None or self._world_scale.device != flag.device):
+            self._world_scale = torch.full((), float(pdist.world_size()), dtype=torch.float32, device=flag.device)
+        return flag, (self._world_scale if in_opt else None)
+
+    def _step_optimizer(self, one_step: Dict[str, Any]):
+        """optimizer.step() under its one-step arguments (found_inf, grad_scale, fused_clip, flag_log, lr_ahead): attributes for this call only"""
+        opt = self.optimizer
+        for name, value in one_step.items():
+            setattr(opt, name, value)
+        try:
+            opt.step()
+        finally:
+            for name in one_step:
+                delattr(opt, name)
+
     def _finish_device_skip(self, step: int, flag: torch.Tensor):
         """eager tail of a step whose backward has run: NaN flag to the host (asynchronously), gradient all-reduce,
         clipping, optimizer step with on-device skip"""
-        grad_scale = None
-        # K18: clamp + global-norm clipping inside the optimizer launch (psnd_grad_sumsq + psnd_adam_step) when the optimizer can and
+        # clamp + global-norm clipping inside the optimizer launch (psnd_grad_sumsq + psnd_adam_step) when the optimizer can and
         # clip_grad() is the stock one; the averaging over ranks is then the kernel's grad_scale as well
         fused_clip = ((self.grad_clip or self.grad_norm) and getattr(self.optimizer, '_supports_fused_clip', False)
                       and type(self).clip_grad is Trainer.clip_grad and self._optimizer_covers_model())
-        if self._reducer is not None and (pdist.is_dist() or self._reducer.active):      # (active without is_dist: a forced one-rank group)
-            # ONE collective per bucket: the flag sits behind the last bucket (set_flag), and when nothing clips the gradients the
-            # division by the world size is left to the optimizer kernel (grad_scale) instead of a pass over the buckets
-            in_opt = fused_clip or not (self.grad_clip or self.grad_norm)
-            self._reducer.finish(average=not in_opt)
-            # the sum of the ranks' 0 / 1 flags (divided by the world size when the buckets are averaged): psnd_adam_step skips on any
-            # non-zero value and takes it as it is; torch's fused optimizers test `found_inf == 1`, so they get it normalised (two launches)
-            rf = self._reducer.flag
-            raw_ok = rf.dtype == torch.float32 and getattr(self.optimizer, '_supports_flag_log', False)
-            flag = rf.reshape(()) if raw_ok else (rf > 0).to(torch.float32).reshape(())
-            if in_opt:
-                if getattr(self, '_world_scale', None) is None or self._world_scale.device != flag.device:
-                    self._world_scale = torch.full((), float(pdist.world_size()), dtype=torch.float32, device=flag.device)
-                grad_scale = self._world_scale
-        elif self._reducer is not None:
-            self._reducer.finish()
+        flag, grad_scale = self._finish_reduce(flag, fused_clip)
+        one_step = {'found_inf': flag, 'grad_scale': grad_scale}
         if fused_clip:
-            self.optimizer.fused_clip = (self.grad_clip, self.grad_norm)
+            one_step['fused_clip'] = (self.grad_clip, self.grad_norm)
         else:
             self.clip_grad()
-        if not hasattr(self, '_nan_pending'):
-            self._nan_pending = []
         use_ring = bool(getattr(self.optimizer, '_supports_flag_log', False)) and flag.is_cuda
         if use_ring:
-            ring = self._nan_ring()
+            if self._nan_ring_buf is None:
+                self._nan_ring_buf = torch.zeros((self._NAN_RING, 2), dtype=torch.int32).pin_memory()
             if len(self._nan_pending) >= self._NAN_RING - 2:   # the host is a whole ring ahead of the device: let it catch up
                 self._poll_nan_log(block=True)
             self._nan_seq += 1
-            slot, seq = self._nan_seq % self._NAN_RING, self._nan_seq
-            self.optimizer.flag_log = (ring, slot, seq)
+            pending = _RingFlag(step, self._nan_ring_buf, self._nan_seq % self._NAN_RING, self._nan_seq)
+            one_step['flag_log'] = (pending.ring, pending.slot, pending.seq)
         sched = self.scheduler is not None             # (_can_skip_on_device / _train_graph let it here: its steps are chosen on the device)
-        self.optimizer.found_inf = flag
-        self.optimizer.grad_scale = grad_scale
-        try:
-            if sched:
-                if not use_ring:
-                    raise RuntimeError('a scheduler on the device-skip path needs the optimizer on the loss\'s HIP device')
-                self.optimizer.lr_ahead = self._lr_stage(flag.device)      # (may raise what the user's schedule raises)
-            self.optimizer.step()
-        finally:
-            del self.optimizer.found_inf
-            del self.optimizer.grad_scale
-            if fused_clip:
-                del self.optimizer.fused_clip
-            if use_ring:
-                del self.optimizer.flag_log
-            if sched and hasattr(self.optimizer, 'lr_ahead'):
-                del self.optimizer.lr_ahead
+        if sched:
+            if not use_ring:
+                raise RuntimeError('a scheduler on the device-skip path needs the optimizer on the loss\'s HIP device')
+            one_step['lr_ahead'] = self._lr_stage(flag.device)             # (may raise what the user's schedule raises)
+        self._step_optimizer(one_step)
         if sched and not getattr(self.optimizer, 'lr_ahead_used', False):
             # no parameter had a gradient: nothing was launched, nothing counted on the device - this one step is settled on the host
             self._poll_nan_log(block=True)
             if float(flag.item()) > 0:
-                self._log('{} cur step NAN is occured'.format(step))
+                self._log_nan(step)
             else:
                 self.scheduler.step()
             self._lr_state = None                      # (rebuilt from the scheduler's state at the next step)
             return
-        if use_ring and getattr(self.optimizer, 'flag_logged', False):
-            self._nan_pending.append((step, slot, seq))    # written by the optimizer launch itself
-        else:
-            # the flag goes to the host BEHIND the optimizer launch (which reads it on the device): the copy is off the step's critical path
-            host_flag = torch.empty((), dtype=torch.float32, pin_memory=True)
-            host_flag.copy_(flag, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-            self._nan_pending.append((step, host_flag, event))
+        if not (use_ring and getattr(self.optimizer, 'flag_logged', False)):   # (else the optimizer launch has written it itself)
+            pending = _CopiedFlag(step, flag)
+        self._nan_pending.append(pending)
         self._poll_nan_log()
 
     # Python's cyclic collector walks every tracked object of the process in a full (generation-2) pass: with torch, numpy and a model
@@ -1039,10 +1034,11 @@ class Trainer:
     gc_freeze = True
     _gc_frozen = False
     _gc_freeze_after = 4
+    _steps_seen = 0
 
     def _maybe_freeze_gc(self):
         if self.gc_freeze and not self._gc_frozen:             # (per Trainer: what a later Trainer of the process builds is frozen after ITS first steps)
-            self._steps_seen = getattr(self, '_steps_seen', 0) + 1
+            self._steps_seen += 1
             if self._steps_seen > self._gc_freeze_after:
                 import gc
                 gc.collect()
@@ -1068,33 +1064,24 @@ class Trainer:
 
         if self._can_skip_on_device(loss):
             self._train_device_skip(step, loss)
-            if log_flag and pdist.is_main():
-                self.console_log('train', meta, step)
-                try:
-                    self.tensorboard_log('train', meta, step)
-                except OverflowError:
-                    pass
-            return
+        else:
+            self.sync_scheduler()                      # (steps of the device-skip path still in flight take their scheduler steps first)
+            if self._loss_is_nan(loss):
+                self._log_nan(step)
+                return
 
-        self.sync_scheduler()                          # (steps of the device-skip path still in flight take their scheduler steps first)
-        if self._loss_is_nan(loss):
-            self._log('{} cur step NAN is occured'.format(step))
-            return
-
-        loss.backward()
-        if self._reducer is not None:
-            self._reducer.finish()
-        self.clip_grad()
-        self.optimizer.step()
-        if self.scheduler is not None:
-            self.scheduler.step()
+            loss.backward()
+            if self._reducer is not None:
+                self._reducer.finish()
+            self.clip_grad()
+            self.optimizer.step()
+            if self.scheduler is not None:
+                self.scheduler.step()
 
         if log_flag and pdist.is_main():
             self.console_log('train', meta, step)
-            try:
+            with contextlib.suppress(OverflowError):
                 self.tensorboard_log('train', meta, step)
-            except OverflowError:
-                pass
 
     def validate(self, step: int):
         self._poll_nan_log(block=True)

@@ -47,7 +47,7 @@ def _trainer(fwd, opt_cls=torch.optim.Adam, pre=None, **attrs):
 
 
 def _captured(tr):
-    return any('graph' in v for v in getattr(tr, '_graphs', {}).values())
+    return any(v.captured for v in getattr(tr, '_graphs', {}).values())
 
 
 def test_pure_forward_is_captured_by_default_and_trains_like_eager():

@@ -191,7 +191,7 @@ def _reducer_worker(port, q):
                     tr.step = i
                     tr.train(i)
                 torch.cuda.synchronize()
-                modes = [v.get('ddp') for v in getattr(tr, '_graphs', {}).values() if 'graph' in v]
+                modes = [v.ddp for v in getattr(tr, '_graphs', {}).values() if v.captured]
                 red = tr._reducer
                 out[(branches, nstep)] = ({k: p.grad.detach().float().cpu().numpy().copy() for k, p in g.named_parameters()} if nstep == 2 else
                                           {k: v.detach().float().cpu().numpy() for k, v in g.state_dict().items()},

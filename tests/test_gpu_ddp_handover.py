@@ -75,7 +75,7 @@ def _worker(port, tmp, q, mode, graph):
         torch.cuda.synchronize()
         if use_ddp:
             red = tr._reducer
-            info = {'modes': [v.get('ddp') for v in getattr(tr, '_graphs', {}).values() if 'graph' in v],
+            info = {'modes': [v.ddp for v in getattr(tr, '_graphs', {}).values() if v.captured],
                     'emit': list(getattr(red, 'emit_log', [])), 'handover': list(red.handover_log),
                     'nb': len(red.buckets), 'nparams': len(red.params), 'sizes': [len(b['params']) for b in red.buckets]}
             dist.destroy_process_group()

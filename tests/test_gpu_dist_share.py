@@ -79,7 +79,7 @@ def _run(rank, world, port, tmp, q, graph, hip_adam, share=True, clip=False):
     torch.cuda.synchronize()
     out = {k: v.cpu().numpy() for k, v in net.state_dict().items()}
     # the mode every captured step graph REALLY ran with (a fallback must be visible to the test), and the backend
-    out['__modes__'] = np.asarray([str(v.get('ddp')) for v in getattr(tr, '_graphs', {}).values() if 'graph' in v])
+    out['__modes__'] = np.asarray([str(v.ddp) for v in getattr(tr, '_graphs', {}).values() if v.captured])
     out['__backend__'] = np.asarray(dist.get_backend())
     q.put((rank, out))
     dist.barrier()
@@ -201,7 +201,7 @@ def _capture_worker(port, tmp, q, use_ddp):
         torch.cuda.synchronize()
         if use_ddp:
             red = tr._reducer
-            info = {'modes': [v.get('ddp') for v in tr._graphs.values() if 'graph' in v], 'emit': list(red.emit_log),
+            info = {'modes': [v.ddp for v in tr._graphs.values() if v.captured], 'emit': list(red.emit_log),
                     'nb': len(red.buckets), 'nparams': len(red.params), 'sizes': [len(b['params']) for b in red.buckets]}
             dist.destroy_process_group()
         q.put((use_ddp, info, {k: v.cpu().numpy() for k, v in net.state_dict().items()}))
@@ -294,7 +294,7 @@ def _gan_train(rank, world, tmp, graph, steps=4):
         tr.train(i)
     torch.cuda.synchronize()
     out = {k: v.detach().float().cpu().numpy() for k, v in g.state_dict().items()}
-    out['__modes__'] = np.asarray([str(v.get('ddp')) for v in getattr(tr, '_graphs', {}).values() if 'graph' in v])
+    out['__modes__'] = np.asarray([str(v.ddp) for v in getattr(tr, '_graphs', {}).values() if v.captured])
     return out
 
 

@@ -162,7 +162,7 @@ def test_fast_path_with_a_scheduler_equals_the_synchronous_loop(tmp_path, run_b,
     b = run_b(sched, opt_kind)
     # A really is the fast path: the step was captured, no host check (this is what fails without the feature)
     assert 'captured the training step as a hipGraph' in a['log']
-    assert a['tr']._lr_state is not None and int(a['tr']._lr_state['count'].item()) == STEPS - len(NAN_AT)
+    assert a['tr']._lr_state is not None and int(a['tr']._lr_state.count.item()) == STEPS - len(NAN_AT)
     assert isinstance(a['tr'].optimizer, poptim.Adam) and isinstance(b['tr'].optimizer, poptim.Adam)
     assert getattr(a['tr'].optimizer.step, '_wrapped_by_lr_sched', False)
     assert b['tr'].host_checks == STEPS and 'hipGraph' not in b['log']
@@ -185,7 +185,7 @@ def test_a_host_that_lags_catches_up_by_blocking(tmp_path, run_b, ring):
     a = _run(tmp_path, 'StepLR', 'own', lazy_host=True, _LR_RING=ring)
     _same(a, run_b('StepLR', 'own'))
     assert a['tr'].block_polls >= (4 if ring == 8 else 1)
-    assert a['tr']._lr_state['ring'].shape == (ring, 2)
+    assert a['tr']._lr_state.ring.shape == (ring, 2)
 
 
 def test_look_ahead_past_the_end_of_a_schedule(tmp_path):
@@ -310,7 +310,7 @@ def _ddp_worker(rank, world, port, tmp, q):
         tr.run()
         torch.cuda.synchronize()
         out = {'params': [p.detach().cpu().numpy() for p in net.parameters()], 'sched': sch.state_dict(), 'lr': opt.param_groups[0]['lr'],     # (numpy: pickled by value)
-               'count': int(tr._lr_state['count'].item()), 'graphs': sum(1 for v in tr._graphs.values() if 'graph' in v),
+               'count': int(tr._lr_state.count.item()), 'graphs': sum(1 for v in tr._graphs.values() if v.captured),
                'steps': [float(opt.state[p]['step']) for p in net.parameters()]}
         q.put((rank, out))
         dist.barrier()

@@ -6,7 +6,7 @@ import tempfile
 import torch
 import torch.nn as nn
 
-from pytorch_sound_amd.trainer import Trainer, LogType, model_fingerprint
+from pytorch_sound_amd.trainer import CapturedStep, Trainer, LogType, model_fingerprint
 
 
 def _net():
@@ -89,16 +89,16 @@ def _trainer(net, log_interval=10 ** 6):
 
 
 def test_trainer_drops_its_graphs_when_the_fingerprint_changes():
-    """the method around the pure function, with stand-ins for captured steps (no GPU here: a record without a 'graph' key is a warm-up
+    """the method around the pure function, with stand-ins for captured steps (no GPU here: a record without a graph is a warm-up
     counter, and that is all reset_graphs looks at before it forgets them)"""
     net = _net()
     tr = _trainer(net)
     tr.train(1)
     assert tr._model_fp == _fp(net)
-    tr._graphs = {'sig': {'seen': 2}}
+    tr._graphs = {'sig': CapturedStep(seen=2)}
     tr._opt_cover = ('key', True)
     tr.train(2)                                                  # nothing toggled: graphs, counters and cache stay
-    assert tr._graphs == {'sig': {'seen': 2}} and tr._opt_cover == ('key', True)
+    assert tr._graphs == {'sig': CapturedStep(seen=2)} and tr._opt_cover == ('key', True)
 
     assert all(p.grad is not None for p in net.parameters())
     w = net[0].weight
@@ -109,13 +109,13 @@ def test_trainer_drops_its_graphs_when_the_fingerprint_changes():
     assert w.grad is None and torch.equal(w, kept), 'frozen: no gradient, not stepped'
     assert all(p.grad is not None for p in net.parameters() if p.requires_grad)
 
-    tr._graphs = {'sig': {'seen': 1}}
+    tr._graphs = {'sig': CapturedStep(seen=1)}
     net[1].eval()
     tr.train(4)
     assert tr._graphs == {}
-    tr._graphs = {'sig': {'seen': 1}}
+    tr._graphs = {'sig': CapturedStep(seen=1)}
     tr.train(5)
-    assert tr._graphs == {'sig': {'seen': 1}}, 'the same state as at the last step'
+    assert tr._graphs == {'sig': CapturedStep(seen=1)}, 'the same state as at the last step'
 
     tr.graph_steps = 'auto'
     assert tr._graph_auto_ok is not False, "a toggle does not switch graph_steps = 'auto' off"
@@ -126,7 +126,7 @@ def test_reset_graphs_on_request_and_frozen_gradients():
     tr = _trainer(net)
     net[2].bias.requires_grad_(False)
     net[2].bias.grad = torch.ones_like(net[2].bias)              # left over from before the Trainer saw the model
-    tr._graphs = {'sig': {'seen': 3}}
+    tr._graphs = {'sig': CapturedStep(seen=3)}
     tr._opt_cover = ('key', False)
     tr.reset_graphs()
     assert tr._graphs == {} and tr._opt_cover is None
@@ -143,6 +143,6 @@ def test_a_module_added_between_steps_is_seen_on_a_logging_step():
     tr.train(1)
     n = len(tr._model_fp[1])
     net.add_module('extra', nn.Identity())
-    tr._graphs = {'sig': {'seen': 1}}
+    tr._graphs = {'sig': CapturedStep(seen=1)}
     tr.train(2)                                                  # a logging step: the model is walked again
     assert len(tr._model_fp[1]) == n + 1 and tr._graphs == {}

@@ -113,7 +113,7 @@ def main():
     audio = float(torch.stack(secs).sum())
     print('config 4 (%s, dropout %g): %.2f ms/step, %.1f k audio-s/s (unpadded); %d step graphs cached' % (
         'hipGraph' if tr.graph_steps else 'eager', DROPOUT, dt / steps * 1e3, audio / dt / 1e3,
-        len([1 for v in getattr(tr, '_graphs', {}).values() if 'graph' in v])))
+        len([1 for v in getattr(tr, '_graphs', {}).values() if v.captured])))
 
 
 if __name__ == '__main__':

@@ -78,7 +78,7 @@ def main():
             tr.sync_scheduler()
         b = blocks[v]
         rows[v] = {'ms_per_step': sum(b) / len(b), 'block_min_ms': min(b), 'block_max_ms': max(b), 'blocks': b,
-                   'captured': any('graph' in s for s in getattr(tr, '_graphs', {}).values()),
+                   'captured': any(s.captured for s in getattr(tr, '_graphs', {}).values()),
                    'scheduler_steps': None if tr.scheduler is None else tr.scheduler.last_epoch, 'trainer_steps': tr.step}
         print('%-16s %8.3f ms/step   blocks %.3f .. %.3f   %s' % (v, rows[v]['ms_per_step'], min(b), max(b),
                                                                  'hipGraph replay' if rows[v]['captured'] else 'eager launches'))
