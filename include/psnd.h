@@ -639,6 +639,31 @@ int psnd_volnorm_fwd(const float *wav, int64_t B, int64_t L, int window, int hop
 int psnd_volnorm_reverse(const float *wav, int64_t B, int64_t L, int window, int hop, float gain, const float *std,
                          float *out, int64_t out_len, void *stream);
 
+/* ---- utils/sound.py: preemphasis / inv_preemphasis (:66-71, scipy.signal.lfilter on the host) and lowpass (:25-35) as one recursive
+ *  filter section of order <= 2 on device tensors (psnd_lfilter.hip) ------------------------------------------------------------------
+ *  psnd_lfilter: per row of x, y : (N, T) fp32, coefficients already divided by a0:
+ *        y[t] = b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2],  zero state before t = 0  (scipy's lfilter with zi = None).
+ *      reverse = 1: the same filter mirrored in time (t+k for t-k, zero state beyond T-1) - the adjoint, i.e. the input gradient.
+ *      The recurrence is held as a two-element state (direct form II transposed) in fp64; the coefficients are plain doubles passed by
+ *      value, so a call can be captured.  `instance`:
+ *        PSND_LFILTER_PARALLEL: an exact scan over time.  A lane walks PSND_LFILTER_CHUNK samples from the zero state; end states combine
+ *            as s_out = M^len s_in + r, M = [[-a1, 1], [-a2, 0]], across the lanes of a wave by shuffles, across the waves of a workgroup
+ *            through LDS, and across the workgroups of a row (one per PSND_LFILTER_SPAN samples) through `carry` and a launch boundary:
+ *            the first launch writes every span's zero-state end state, the second folds the ones before its span and walks again.  No
+ *            workgroup waits on another inside a launch.  The caller's rule: this instance whenever every entry of M^PSND_LFILTER_SPAN
+ *            is finite (any pole inside or on the unit circle, and outside it as far as the power stays finite);
+ *        PSND_LFILTER_SEQ: one lane per row, for every other filter (and for NaN coefficients).
+ *      carry : N * psnd_lfilter_spans(T) * 2 doubles of scratch for the parallel instance (every entry read is written first; may be
+ *      NULL for PSND_LFILTER_SEQ).  x != y.  N == 0 or T == 0: nothing to do.
+ *  psnd_lfilter_spans(T): ceil(T / PSND_LFILTER_SPAN), 0 for T <= 0 (host helper). */
+#define PSND_LFILTER_SPAN 8192
+#define PSND_LFILTER_CHUNK 32
+#define PSND_LFILTER_PARALLEL 0
+#define PSND_LFILTER_SEQ 1
+int64_t psnd_lfilter_spans(int64_t T);
+int psnd_lfilter(const float *x, int64_t N, int64_t T, double b0, double b1, double b2, double a1, double a2, int reverse,
+                 int instance, double *carry, float *y, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

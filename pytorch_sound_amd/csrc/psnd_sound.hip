@@ -32,18 +32,17 @@
 // VolNormConv: one workgroup per hop; unbiased standard deviation of ALL B * window elements of wav[..., start : start + window] in two
 // passes (mean, then squared deviations) accumulated in double, then the hop's own output slice.
 #include "psnd_common.h"
+#include "psnd_span_stage.h"
 #include <math.h>
 
 namespace {
 
-constexpr int LANES = 256;
+constexpr int LANES = STAGE_LANES;                     // pitched, stage_in, stage_out: psnd_span_stage.h
 constexpr int CH = 32;                                  // samples per lane
 constexpr int SPAN = PSND_IPREEMPH_SPAN;                // samples per workgroup
 constexpr int WARM_MAX = PSND_IPREEMPH_WARM_MAX;
 constexpr int IMG = (SPAN + WARM_MAX) / 32 * 33;        // words of one pitched LDS image
 static_assert(SPAN == LANES * CH && CH == 32 && WARM_MAX % 32 == 0, "geometry");
-
-__device__ __forceinline__ int pitched(int i) { return i + (i >> 5); }
 
 // the rule: smallest multiple of 32 with 2 |w_hh|^W <= 2^-25, or PSND_IPREEMPH_SEQ
 __device__ __forceinline__ int warm_rule(float w_hh) {
@@ -68,44 +67,6 @@ __device__ __forceinline__ double block_sum_d(double v, double *red) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// s[pos(i)] = src[t0 + i] for i in [0, n), n % 4 == 0, zeros where t0 + i is outside [0, T).  PITCH: pitched image, else plain.
-template <bool PITCH>
-__device__ __forceinline__ void stage_in(float *s, const float *row, long long T, long long t0, int n) {
-    for (int i = 4 * threadIdx.x; i < n; i += 4 * LANES) {
-        const long long t = t0 + i;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (t >= 0 && t + 3 < T) {
-            v = *reinterpret_cast<const f32x4_u *>(row + t);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (t + k >= 0 && t + k < T) v[k] = row[t + k];
-        }
-        const int p = PITCH ? pitched(i) : i;           // i % 4 == 0: the four words stay inside one group of 32
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[p + k] = v[k];
-    }
-}
-// dst[t0 + i] = s[pos(i0 + i)] for i in [0, n), n % 4 == 0, i0 % 4 == 0, where t0 + i < T   (t0 >= 0)
-template <bool PITCH>
-__device__ __forceinline__ void stage_out(const float *s, int i0, float *row, long long T, long long t0, int n) {
-    for (int i = 4 * threadIdx.x; i < n; i += 4 * LANES) {
-        const long long t = t0 + i;
-        if (t >= T) break;
-        const int p = PITCH ? pitched(i0 + i) : i0 + i;
-        f32x4 v;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = s[p + k];
-        if (t + 3 < T) {
-            *reinterpret_cast<f32x4_u *>(row + t) = v;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (t + k < T) row[t + k] = v[k];
-        }
-    }
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------

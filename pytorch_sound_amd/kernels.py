@@ -2,7 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.
+or a missing library raises.  (`lfilter` alone also takes CPU tensors: there the reference's
+own scipy call IS the implementation; a HIP tensor never reaches it.)
 """
 import math
 import os
@@ -1120,6 +1121,94 @@ class InversePreEmphasisFn(torch.autograd.Function):
                                           stream_ptr(x.device)), 'psnd_ipreemph_bwd')
         need = ctx.needs_input_grad
         return (gx if need[0] else None, gw[0].reshape(w_ih.shape) if need[1] else None, gw[1].reshape(w_hh.shape) if need[2] else None, None)
+
+
+LFILTER_SPAN, LFILTER_PARALLEL, LFILTER_SEQ = 8192, 0, 1        # include/psnd.h
+
+
+def lfilter_section(b, a):
+    """(b0, b1, b2, a1, a2): the coefficients of one section of order <= 2 divided by a[0] in float64, missing ones zero"""
+    b, a = np.asarray(b, dtype=np.float64).ravel().tolist(), np.asarray(a, dtype=np.float64).ravel().tolist()
+    if not 1 <= len(b) <= 3 or not 1 <= len(a) <= 3:
+        raise _lib.PsndError('lfilter: %d numerator and %d denominator coefficients - sections of order <= 2 (at most three each) are covered'
+                             % (len(b), len(a)))
+    if a[0] == 0.0:
+        raise ValueError('lfilter: a[0] must not be zero')
+    b, a = [v / a[0] for v in b] + [0.0] * (3 - len(b)), [v / a[0] for v in a] + [0.0] * (3 - len(a))
+    return b[0], b[1], b[2], a[1], a[2]
+
+
+def lfilter_instance(b, a):
+    """the instance of psnd_lfilter for this filter (the rule of include/psnd.h, host numbers only): LFILTER_PARALLEL while every entry of
+    M^8192, M = [[-a1, 1], [-a2, 0]], is finite - every pole inside or on the unit circle, and outside it as far as the power stays
+    finite; LFILTER_SEQ otherwise and for coefficients that are not finite."""
+    sec = lfilter_section(b, a)
+    if not all(math.isfinite(v) for v in sec):
+        return LFILTER_SEQ
+    m = (-sec[3], 1.0, -sec[4], 0.0)
+    for _ in range(13):                                  # 2^13 = 8192, by squaring as the library does
+        m = (m[0] * m[0] + m[1] * m[2], m[0] * m[1] + m[1] * m[3], m[2] * m[0] + m[3] * m[2], m[2] * m[1] + m[3] * m[3])
+    return LFILTER_PARALLEL if all(math.isfinite(v) for v in m) else LFILTER_SEQ
+
+
+def _lfilter_rows(x, sec, reverse, instance):
+    if x.dim() == 0:
+        raise _lib.PsndError('lfilter: the input needs a time axis')
+    if not x.is_cuda:                                    # the reference's own path: scipy on the host, in float64
+        from scipy.signal import lfilter as host_lfilter
+        if not x.is_floating_point():
+            raise _lib.PsndError('lfilter: floating input expected, got %s' % x.dtype)
+        if x.numel() == 0:
+            return torch.empty_like(x)
+        v = x.detach().to(torch.float64).numpy()
+        v = v[..., ::-1] if reverse else v
+        y = host_lfilter(sec[:3], (1.0,) + sec[3:], v, axis=-1)
+        return torch.from_numpy(np.ascontiguousarray(y[..., ::-1] if reverse else y)).to(x.dtype)
+    if x.dtype == torch.float64:
+        raise _lib.PsndError('lfilter: no float64 instance on HIP tensors (a round trip through float32 would silently lose the precision '
+                             'asked for): filter a float32 tensor, or a CPU tensor in float64')
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.PsndError('lfilter: floating input expected, got %s' % x.dtype)
+    xf = x.detach().contiguous().float()
+    T = xf.shape[-1]
+    N = xf.numel() // max(T, 1)
+    y = torch.empty_like(xf)
+    carry = None
+    if instance == LFILTER_PARALLEL:
+        carry = torch.empty(2 * N * int(lib().psnd_lfilter_spans(T)), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().psnd_lfilter(ptr(xf), N, T, *sec, int(bool(reverse)), int(instance), ptr(carry), ptr(y), stream_ptr(x.device)), 'psnd_lfilter')
+    return y.to(x.dtype)
+
+
+class LFilterFn(torch.autograd.Function):
+    """one filter section on the last axis; the gradient is the same Function mirrored in time, so nothing is saved and it composes for a
+    second derivative"""
+
+    @staticmethod
+    def forward(ctx, x, sec, reverse, instance):
+        ctx.sec, ctx.reverse, ctx.instance = sec, reverse, instance
+        return _lfilter_rows(x, sec, reverse, instance)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return LFilterFn.apply(gy, ctx.sec, not ctx.reverse, ctx.instance), None, None, None
+
+
+def lfilter(x, b, a, reverse=False, instance=None):
+    """scipy.signal.lfilter(b, a, x) with zero initial state along the last axis of a tensor of any shape (..., T), for a section of order
+    <= 2: y[t] = (b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2]) / a0.  `reverse`: the same filter mirrored in time (the adjoint).
+
+    HIP tensors run psnd_lfilter (float32; float16 / bfloat16 are cast in and out; float64 raises), CPU tensors scipy in float64 - the one
+    entry of this module with a host path, because the reference's own implementation is that scipy call.  Differentiable in x on both
+    devices; `b` and `a` are plain numbers and carry no gradient.  `instance`: LFILTER_PARALLEL or LFILTER_SEQ instead of the rule of
+    `lfilter_instance` (HIP tensors only)."""
+    sec = lfilter_section(b, a)
+    if instance is None:
+        instance = lfilter_instance(b, a)
+    elif instance not in (LFILTER_PARALLEL, LFILTER_SEQ):
+        raise _lib.PsndError('lfilter: instance=%r' % (instance,))
+    return LFilterFn.apply(x, sec, bool(reverse), instance)
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

@@ -1,0 +1,86 @@
+"""pytorch_sound/utils/sound.py: the filters, on numpy arrays as the reference has them and on tensors of either device.
+
+    preemphasis, inv_preemphasis   the reference's two scipy.signal.lfilter calls (:66-71)
+    lowpass, highpass, biquad      two-pole sections (the reference's lowpass pipes the array through sox, :25-35)
+    get_wav_duration               :52-63
+
+A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
+device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
+no host round trip, no library op), on a CPU tensor scipy in float64.  All filters run along the last axis with zero initial state.
+
+Not here: `parse_midi` (pretty_midi) and `get_f0` (pyworld, librosa) - host-only wrappers around packages this project does not depend on.
+
+`lowpass` is NOT pinned against the reference: its output there is whatever the installed sox computes (through pysndfx), which this
+project cannot run.  What is implemented is the two-pole low-pass of the Audio EQ Cookbook, the design sox documents for its `lowpass`
+effect, in floating point without sox's clipping at full scale; the tests check it by known answers (DC gain, -3 dB at the cutoff),
+not against sox output.  The defaults (44.1 kHz, q = 0.707) are pysndfx's as remembered, not verified.
+"""
+import math
+
+import numpy as np
+from scipy import signal
+from scipy.io.wavfile import read as wav_read
+
+from .. import kernels
+
+
+def _is_tensor(x):
+    import torch
+    return isinstance(x, torch.Tensor)
+
+
+def biquad(x, b, a):
+    """one filter section of order <= 2 along the last axis, zero initial state: scipy.signal.lfilter(b, a, x).  numpy in -> float32 numpy
+    out (as the reference's filters); tensor in -> tensor of the same dtype and device out."""
+    if _is_tensor(x):
+        return kernels.lfilter(x, b, a)
+    kernels.lfilter_section(b, a)                       # the same argument checks on both paths
+    return signal.lfilter(b, a, x).astype(np.float32)
+
+
+def preemphasis(x, coeff=0.97):
+    """y[t] = x[t] - coeff x[t-1] with x[-1] = 0 (sound.py:66-67).  `models.sound.PreEmphasis` reflect-pads one sample instead (x[-1] = x[1]):
+    the two differ in sample 0 only."""
+    return biquad(x, [1, -coeff], [1])
+
+
+def inv_preemphasis(x, coeff=0.97):
+    """y[t] = x[t] + coeff y[t-1] with y[-1] = 0 (sound.py:70-71): the exact inverse of `preemphasis`.  (`models.sound.InversePreEmphasis`
+    is the reference's tanh RNN, not this filter.)"""
+    return biquad(x, [1], [1, -coeff])
+
+
+def _cookbook(frequency, sample_rate, q):
+    w0 = 2.0 * math.pi * float(frequency) / float(sample_rate)
+    return math.cos(w0), math.sin(w0) / (2.0 * float(q))
+
+
+def lowpass_coefficients(frequency, sample_rate=44100, q=0.707):
+    """(b, a) of the Audio EQ Cookbook two-pole low-pass: w0 = 2 pi f / fs, alpha = sin w0 / (2 q)"""
+    c, alpha = _cookbook(frequency, sample_rate, q)
+    return [(1 - c) / 2, 1 - c, (1 - c) / 2], [1 + alpha, -2 * c, 1 - alpha]
+
+
+def highpass_coefficients(frequency, sample_rate=44100, q=0.707):
+    """(b, a) of the cookbook two-pole high-pass, the mirror image of the low-pass"""
+    c, alpha = _cookbook(frequency, sample_rate, q)
+    return [(1 + c) / 2, -(1 + c), (1 + c) / 2], [1 + alpha, -2 * c, 1 - alpha]
+
+
+def lowpass(wav, frequency, sample_rate=44100, q=0.707):
+    """two-pole low-pass at `frequency` Hz (sound.py:25-35).  Parity with the reference's sox output is unpinned: module docstring."""
+    return biquad(wav, *lowpass_coefficients(frequency, sample_rate, q))
+
+
+def highpass(wav, frequency, sample_rate=44100, q=0.707):
+    """two-pole high-pass at `frequency` Hz; not in the reference, the counterpart of `lowpass`"""
+    return biquad(wav, *highpass_coefficients(frequency, sample_rate, q))
+
+
+def get_wav_duration(file):
+    """duration of a wave file in seconds, -1 where it cannot be read (sound.py:52-63)"""
+    try:
+        sr, wav = wav_read(file)
+        return len(wav) / sr
+    except Exception:      # noqa: BLE001 - the reference swallows everything here
+        return -1
