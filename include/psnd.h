@@ -664,6 +664,31 @@ int64_t psnd_lfilter_spans(int64_t T);
 int psnd_lfilter(const float *x, int64_t N, int64_t T, double b0, double b1, double b2, double a1, double a2, int reverse,
                  int instance, double *carry, float *y, void *stream);
 
+/* ---- sample-rate conversion by a rational factor up / down on device tensors (psnd_resample.hip): what the reference leaves to sox
+ *  (scripts/preprocess.py:82-88) and ffmpeg (:32-41).  The definition is scipy.signal.resample_poly's with zero padding -----------------
+ *  psnd_resample: per row of x : (N, T) fp32 into y : (N, T_out) fp32, with P = (taps - 1) / 2 and h the `taps` fp32 filter values
+ *  (designed in float64 on the host and rounded once; scipy's firwin(2P+1, 1/max(up,down), ('kaiser', 5.0)) * up for P = 10 max(up, down)):
+ *        y[n][m] = sum_i x[n][i] g[m down - i up + P],   0 <= m < T_out,  over 0 <= i < T with 0 <= m down - i up + P <= 2P,
+ *        g = h (flip 0) or h reversed (flip 1).
+ *      The forward conversion is (up, down, flip 0, T_out = psnd_resample_len(T, up, down)).  Its adjoint - the input gradient - is the same
+ *      call with up and down exchanged, flip 1, the gradient as x and T_out = the length of the forward input: one kernel, both ways.
+ *      T_out is the caller's: outputs that no input reaches are written as zeros.
+ *      h is read as given, in natural order (no packed plan): a workgroup of 256 lanes owns PSND_RESAMPLE_TILE consecutive outputs of one
+ *      row, keeps g whole in LDS (reversed while loading for flip 1; output m reads g[phi + j up], phi = (m down + P) mod up, and
+ *      neighbouring lanes differ in phi by down mod up words) and stages the span of x that its tile reaches through LDS in pieces of
+ *      3072 samples.  Products are accumulated in fp32 from the newest input sample to the oldest; no atomics, the same bits every run.
+ *      All loads and stores are single dwords: rows may start at any 4-byte boundary.  Every element of y[0 .. N T_out) is written,
+ *      nothing else.  x != y.  N == 0 or T_out == 0: nothing to do; T == 0 with T_out > 0 writes zeros (x may then be NULL).
+ *      taps must be odd, positive and at most PSND_RESAMPLE_MAX_TAPS (12801: 11.025 kHz <-> 16 / 48 kHz, the widest pair among the
+ *      usual audio rates; g and the staged span share 64 KB of LDS); up, down > 0; sizes >= 0.  Bad arguments return PSND_E_ARG (more
+ *      than 2^31 - 1 workgroups: PSND_E_SHAPE) before anything is launched.
+ *  psnd_resample_len(T, up, down): ceil(T up / down), 0 for T <= 0 or a non-positive factor (host helper). */
+#define PSND_RESAMPLE_TILE 1024
+#define PSND_RESAMPLE_MAX_TAPS 12801
+int64_t psnd_resample_len(int64_t T, int up, int down);
+int psnd_resample(const float *x, int64_t N, int64_t T, const float *h, int taps, int up, int down, int flip, float *y, int64_t T_out,
+                  void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

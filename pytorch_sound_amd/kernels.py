@@ -2,8 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter` alone also takes CPU tensors: there the reference's
-own scipy call IS the implementation; a HIP tensor never reaches it.)
+or a missing library raises.  (`lfilter` and `resample_poly` alone also take CPU tensors: there the
+scipy call IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
 import os
@@ -1209,6 +1209,167 @@ def lfilter(x, b, a, reverse=False, instance=None):
     elif instance not in (LFILTER_PARALLEL, LFILTER_SEQ):
         raise _lib.PsndError('lfilter: instance=%r' % (instance,))
     return LFilterFn.apply(x, sec, bool(reverse), instance)
+
+
+RESAMPLE_TILE, RESAMPLE_MAX_TAPS = 1024, 12801                  # include/psnd.h
+
+
+def resample_ratio(orig_sr, new_sr):
+    """(up, down) of a conversion from orig_sr to new_sr Hz, divided by their gcd.  Integer rates only: anything else, and a rate <= 0,
+    raises ValueError."""
+    rates = []
+    for name, v in (('orig_sr', orig_sr), ('new_sr', new_sr)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError('resample: %s=%r - integer sample rates only' % (name, v))
+        if v <= 0:
+            raise ValueError('resample: %s=%r must be positive' % (name, v))
+        rates.append(int(v))
+    g = math.gcd(*rates)
+    return rates[1] // g, rates[0] // g
+
+
+def _resample_factors(up, down):
+    for name, v in (('up', up), ('down', down)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError('resample: %s=%r - a positive integer factor' % (name, v))
+    g = math.gcd(int(up), int(down))
+    return int(up) // g, int(down) // g
+
+
+def resample_taps(up, down):
+    """the filter of scipy.signal.resample_poly(x, up, down) in float64, gain included: P = 10 max(up, down) for the reduced factors and
+    h = firwin(2P + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up.  Equal factors have no filter to design (scipy returns a copy):
+    the one tap 1."""
+    from scipy.signal import firwin
+    up, down = _resample_factors(up, down)
+    big = max(up, down)
+    if big == 1:
+        return np.ones(1)
+    return firwin(2 * 10 * big + 1, 1.0 / big, window=('kaiser', 5.0)) * up
+
+
+class ResampleTaps:
+    """the filter of one conversion: `h`, the float64 values that are applied (gain included), `window`, what scipy.signal.resample_poly
+    takes as `window=` for them, and the float32 copy of h per device, made on first use and kept - a later call copies nothing from the
+    host and can be captured into a graph."""
+
+    def __init__(self, h, window):
+        self.h = np.ascontiguousarray(h, dtype=np.float64)
+        self.h.setflags(write=False)
+        self.window = window
+        self._on = {}
+
+    def on(self, device):
+        t = self._on.get(device)
+        if t is None:
+            t = self._on[device] = torch.from_numpy(self.h.astype(np.float32)).to(device)
+        return t
+
+
+_RESAMPLE_TAPS = {}
+
+
+def resample_plan(up, down, taps=None):
+    """the cached ResampleTaps of reduced factors (up, down): the default filter, or `taps` as scipy takes an array for `window=` - an
+    odd-length prototype of unit gain that is applied times `up`"""
+    up, down = _resample_factors(up, down)
+    if taps is None:
+        key = (up, down, None)
+    else:
+        w = np.asarray(taps, dtype=np.float64)
+        if w.ndim != 1 or w.size % 2 == 0:
+            raise ValueError('resample: taps must be a sequence of odd length, got shape %s' % (w.shape,))
+        key = (up, down, w.tobytes())
+    plan = _RESAMPLE_TAPS.get(key)
+    if plan is None:
+        plan = _RESAMPLE_TAPS[key] = ResampleTaps(resample_taps(up, down), ('kaiser', 5.0)) if taps is None else ResampleTaps(w * up, w.copy())
+    return plan
+
+
+def _resample_host(v, up, down, plan, flip, out_len):
+    """the definition on a float64 array (..., T): scipy.signal.resample_poly where that is the call, else scipy.signal.upfirdn with the
+    zeros in front of the filter that put output 0 on a multiple of `down`, as resample_poly does inside"""
+    from scipy import signal
+    T = v.shape[-1]
+    if not flip and out_len == -(-T * up // down) and T > 0:
+        return signal.resample_poly(v, up, down, axis=-1, window=plan.window if isinstance(plan.window, tuple) else plan.window.copy())
+    out = np.zeros(v.shape[:-1] + (out_len,), dtype=np.float64)
+    if T == 0 or out_len == 0:
+        return out
+    g = plan.h[::-1] if flip else plan.h
+    P = g.size // 2
+    pre = down - P % down
+    skip = (P + pre) // down
+    full = signal.upfirdn(np.concatenate((np.zeros(pre), g)), v, up, down, axis=-1)[..., skip:skip + out_len]
+    out[..., :full.shape[-1]] = full
+    return out
+
+
+def _resample_rows(x, up, down, plan, flip, out_len, device_taps):
+    T = x.shape[-1]
+    if not x.is_cuda:
+        if x.numel() == 0:
+            return x.new_zeros(x.shape[:-1] + (out_len,))
+        y = _resample_host(x.detach().to(torch.float64).numpy(), up, down, plan, flip, out_len)
+        return torch.from_numpy(np.ascontiguousarray(y)).to(x.dtype)
+    taps = plan.h.size
+    h = plan.on(x.device) if device_taps is None else device_taps
+    if h.device != x.device or h.dtype != torch.float32 or h.numel() != taps or not h.is_contiguous():
+        raise _lib.PsndError('resample: the device taps must be %d contiguous float32 values on %s, got %s %s on %s'
+                             % (taps, x.device, tuple(h.shape), h.dtype, h.device))
+    xf = x.detach().contiguous().float()
+    N = math.prod(xf.shape[:-1])                         # rows, also where T == 0: those write zeros
+    y = torch.empty(xf.shape[:-1] + (out_len,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().psnd_resample(ptr(xf), N, T, ptr(h), taps, up, down, int(bool(flip)), ptr(y), out_len, stream_ptr(x.device)),
+              'psnd_resample')
+    return y.to(x.dtype)
+
+
+class ResampleFn(torch.autograd.Function):
+    """y[m] = sum_i x[i] g[m down - i up + P] on the last axis (include/psnd.h); the gradient is the same Function with up and down
+    exchanged, the taps reversed and the input's length as out_len, so nothing is saved and it composes for a second derivative"""
+
+    @staticmethod
+    def forward(ctx, x, up, down, taps, flip, out_len, device_taps):
+        ctx.args = (up, down, taps, flip, x.shape[-1], device_taps)
+        return _resample_rows(x, up, down, taps, flip, out_len, device_taps)
+
+    @staticmethod
+    def backward(ctx, gy):
+        up, down, taps, flip, T, device_taps = ctx.args
+        return ResampleFn.apply(gy, down, up, taps, not flip, T, device_taps), None, None, None, None, None, None
+
+
+def resample_poly(x, up, down, taps=None, device_taps=None):
+    """scipy.signal.resample_poly(x, up, down) with zero padding along the last axis of a tensor of any shape (..., T): the result has
+    ceil(T up / down) samples (up, down reduced by their gcd; equal factors return a copy).  `taps`: an odd-length sequence instead of the
+    default Kaiser design, as scipy takes an array for `window=` (unit gain; the filter applied is taps * up).
+
+    HIP tensors run psnd_resample (float32; float16 / bfloat16 are cast in and out; float64 raises); the float32 taps live on the device,
+    cached per (up, down, taps, device), or are `device_taps` where the caller keeps them (models.sound.Resample's buffer).  Taps beyond
+    RESAMPLE_MAX_TAPS raise: no host path for a HIP tensor.  CPU tensors go through scipy in float64.  Differentiable in x on both
+    devices, any number of times."""
+    if not isinstance(x, torch.Tensor):
+        raise _lib.PsndError('resample: a tensor is expected, got %s' % type(x).__name__)
+    if x.dim() == 0:
+        raise _lib.PsndError('resample: the input needs a time axis')
+    if not x.is_floating_point():
+        raise _lib.PsndError('resample: floating input expected, got %s' % x.dtype)
+    up, down = _resample_factors(up, down)
+    plan = resample_plan(up, down, taps)
+    if up == down:
+        return x.clone()
+    if x.is_cuda:
+        if x.dtype == torch.float64:
+            raise _lib.PsndError('resample: no float64 instance on HIP tensors (a round trip through float32 would silently lose the '
+                                 'precision asked for): resample a float32 tensor, or a CPU tensor in float64')
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise _lib.PsndError('resample: floating input expected, got %s' % x.dtype)
+        if plan.h.size > RESAMPLE_MAX_TAPS:
+            raise _lib.PsndError('resample: %d taps for the ratio %d / %d, the kernel holds at most RESAMPLE_MAX_TAPS = %d (no host path for '
+                                 'a HIP tensor)' % (plan.h.size, up, down, RESAMPLE_MAX_TAPS))
+    return ResampleFn.apply(x, up, down, plan, False, -(-x.shape[-1] * up // down), device_taps)
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

@@ -1,5 +1,5 @@
 """Drop-in for pytorch_sound/models/sound.py: VolNormConv, PreEmphasis, InversePreEmphasis, build_stft_functions,
-multi_stft_loss - same names, arguments and results.
+multi_stft_loss - same names, arguments and results - and Resample, which the reference does not have.
 
 On a HIP device every class here runs on libpsnd_hip.so (psnd_volnorm_*, psnd_preemphasis_*, psnd_ipreemph_*, psnd_stft_fwd/bwd,
 psnd_stft_loss_*); CPU tensors take the reference's torch formulation (host-side use: tests, data preparation).
@@ -153,6 +153,27 @@ class InversePreEmphasis(torch.nn.Module):
             return y if y.dtype == input.dtype else y.to(input.dtype)
         x, _ = self.rnn(input.transpose(1, 2))
         return x.transpose(1, 2)
+
+
+class Resample(torch.nn.Module):
+    """Sample-rate conversion from ``orig_sr`` to ``new_sr`` Hz (integer rates) on (B, T) or (B, 1, T), no parameters:
+    scipy.signal.resample_poly's definition (``utils.sound.resample``), ceil(T new_sr / orig_sr) samples out.  Not in the reference, which
+    converts files offline through sox or ffmpeg; parity with those is unpinned.  A HIP tensor takes psnd_resample in both directions; the
+    float32 taps are a non-persistent buffer, so ``.to(device)`` carries them, the state dict stays empty and a call can be captured."""
+
+    def __init__(self, orig_sr: int, new_sr: int):
+        super().__init__()
+        self.orig_sr, self.new_sr = orig_sr, new_sr
+        self.up, self.down = K.resample_ratio(orig_sr, new_sr)
+        self.register_buffer('taps', torch.from_numpy(K.resample_taps(self.up, self.down)).float(), persistent=False)
+
+    def forward(self, wav: torch.Tensor) -> torch.Tensor:
+        if wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.size(1) != 1):
+            raise RuntimeError('Resample expects a (B, T) or (B, 1, T) tensor, got %s' % (tuple(wav.shape),))
+        return K.resample_poly(wav, self.up, self.down, device_taps=self.taps if wav.is_cuda else None)
+
+    def extra_repr(self) -> str:
+        return 'orig_sr=%d, new_sr=%d, up=%d, down=%d' % (self.orig_sr, self.new_sr, self.up, self.down)
 
 
 #

@@ -3,6 +3,7 @@
     preemphasis, inv_preemphasis   the reference's two scipy.signal.lfilter calls (:66-71)
     lowpass, highpass, biquad      two-pole sections (the reference's lowpass pipes the array through sox, :25-35)
     get_wav_duration               :52-63
+    resample                       sample-rate conversion (the reference shells out: scripts/preprocess.py:82-88 sox, :32-41 ffmpeg)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -14,6 +15,13 @@ Not here: `parse_midi` (pretty_midi) and `get_f0` (pyworld, librosa) - host-only
 project cannot run.  What is implemented is the two-pole low-pass of the Audio EQ Cookbook, the design sox documents for its `lowpass`
 effect, in floating point without sox's clipping at full scale; the tests check it by known answers (DC gain, -3 dB at the cutoff),
 not against sox output.  The defaults (44.1 kHz, q = 0.707) are pysndfx's as remembered, not verified.
+
+`resample` is NOT pinned against the reference either, for the same reason: there the rate is changed by `sox ... rate` or by ffmpeg, whose
+filters this project can neither run nor read off.  What is implemented is scipy.signal.resample_poly, on which the reference already
+depends through scipy: with up / down = new_sr / orig_sr in lowest terms and P = 10 max(up, down), the linear-phase low-pass
+firwin(2P + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up applied between zero-stuffing by `up` and keeping every `down`-th sample,
+zeros beyond both ends, ceil(T up / down) samples out.  A numpy array goes through scipy itself; a HIP tensor through the polyphase kernel of
+psnd_resample.hip (`kernels.resample_poly`), which is that sum in float32 and whose gradient is the same kernel the other way round.
 """
 import math
 
@@ -75,6 +83,23 @@ def lowpass(wav, frequency, sample_rate=44100, q=0.707):
 def highpass(wav, frequency, sample_rate=44100, q=0.707):
     """two-pole high-pass at `frequency` Hz; not in the reference, the counterpart of `lowpass`"""
     return biquad(wav, *highpass_coefficients(frequency, sample_rate, q))
+
+
+def resample(wav, orig_sr, new_sr):
+    """`wav` at orig_sr Hz converted to new_sr Hz along the last axis (integer rates): scipy.signal.resample_poly's definition, module
+    docstring.  numpy in -> float32 numpy out; tensor in -> tensor of the same dtype and device out.  Equal rates return a copy.  Not pinned
+    against the reference's sox / ffmpeg output."""
+    up, down = kernels.resample_ratio(orig_sr, new_sr)
+    if _is_tensor(wav):
+        return kernels.resample_poly(wav, up, down)
+    wav = np.asarray(wav)
+    if wav.ndim == 0:
+        raise kernels.PsndError('resample: the input needs a time axis')
+    if up == down:
+        return wav.astype(np.float32)                   # a copy, as scipy's
+    if wav.size == 0:
+        return np.zeros(wav.shape[:-1] + (-(-wav.shape[-1] * up // down),), dtype=np.float32)
+    return signal.resample_poly(wav.astype(np.float64), up, down, axis=-1).astype(np.float32)
 
 
 def get_wav_duration(file):

@@ -1,0 +1,245 @@
+"""Sample-rate conversion without a GPU: the definition of tests/resample_ref.py against scipy.signal.resample_poly, the design of the taps,
+the ratio helper, the numpy and CPU-tensor paths of utils.sound.resample with their autograd, the two C ABI entries and their argument
+errors, and the models.sound.Resample module."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+from scipy import signal
+
+import resample_ref as R
+from conftest import ROOT
+
+LENGTHS = (1, 2, 5, 37, 211)
+
+
+@pytest.fixture(scope='module')
+def snd():
+    import pytorch_sound.utils.sound as m
+    return m
+
+
+@pytest.fixture(scope='module')
+def L():
+    from pytorch_sound_amd import _build, _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        _build.build(verbose=False)
+    return _lib
+
+
+def _K():
+    from pytorch_sound_amd import kernels
+    return kernels
+
+
+# ---- definition and design ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('up,down', R.RATIOS)
+def test_direct_sum_is_scipy_resample_poly(up, down):
+    for T in LENGTHS:
+        x = R.signal_rows(T, 4, T).astype(np.float64)
+        want = signal.resample_poly(x, up, down, axis=-1)
+        got = R.resample(x, up, down)
+        assert got.shape == want.shape == (4, R.out_len(T, up, down))
+        assert np.abs(got - want).max() <= 1e-12, (up, down, T)
+    w = np.arange(1.0, 8.0)                                              # an array for window=: scipy applies it times up
+    x = R.signal_rows(9, 2, 37).astype(np.float64)
+    assert np.abs(R.resample(x, up, down, w * up) - signal.resample_poly(x, up, down, axis=-1, window=w)).max() <= 1e-12
+
+
+@pytest.mark.parametrize('up,down', R.RATIOS)
+def test_adjoint_of_the_definition(up, down):
+    for T in LENGTHS:
+        x = R.signal_rows(T + 1, 2, T).astype(np.float64)
+        y = R.resample(x, up, down)
+        g = R.signal_rows(T + 2, 2, y.shape[-1]).astype(np.float64)
+        gx = R.adjoint(g, up, down, T)
+        lhs, rhs = (y * g).sum(), (x * gx).sum()
+        assert abs(lhs - rhs) <= 1e-13 * max(abs(lhs), 1.0)
+        # the same form the other way round: factors exchanged, taps reversed, length given
+        assert np.abs(gx - R.resample(g, down, up, R.taps(up, down)[::-1], T_out=T)).max() <= 1e-13
+
+
+def test_taps_and_ratio():
+    K = _K()
+    for up, down in R.RATIOS:
+        h = K.resample_taps(up, down)
+        assert h.dtype == np.float64 and h.size == 20 * max(up, down) + 1 and np.array_equal(h, R.taps(up, down))
+    assert np.array_equal(K.resample_taps(4, 2), R.taps(2, 1))           # reduced first
+    assert K.resample_ratio(44100, 22050) == (1, 2)
+    assert K.resample_ratio(22050, 16000) == (320, 441)
+    assert K.resample_ratio(48000, 44100) == (147, 160)
+    assert K.resample_ratio(np.int64(16000), 16000) == (1, 1)
+    for bad in ((44100.0, 22050), (22050, 16000.5), (0, 16000), (16000, -1), ('a', 3), (None, 1), (True, 2)):
+        with pytest.raises(ValueError):
+            K.resample_ratio(*bad)
+
+
+# ---- numpy and CPU tensors ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('rates', [(44100, 22050), (22050, 44100), (22050, 16000), (16000, 22050), (48000, 44100), (32000, 48000)])
+def test_numpy_and_cpu_tensor_paths(snd, rates):
+    K = _K()
+    up, down = K.resample_ratio(*rates)
+    x = R.signal_rows(3, 6, 211).reshape(2, 3, 211)
+    want = R.resample(x, up, down)
+    got = snd.resample(x, *rates)
+    assert isinstance(got, np.ndarray) and got.dtype == np.float32 and got.shape == (2, 3, R.out_len(211, up, down))
+    assert np.abs(got - want).max() <= 2.0 ** -23 * max(np.abs(want).max(), 1.0)
+    assert snd.resample(x.astype(np.float64)[0, 0], *rates).shape == (R.out_len(211, up, down),)
+    for dtype, tol in ((torch.float64, 1e-12), (torch.float32, 2.0 ** -22), (torch.bfloat16, 2.0 ** -7)):
+        t = snd.resample(torch.from_numpy(x).to(dtype), *rates)
+        assert isinstance(t, torch.Tensor) and t.dtype == dtype and t.device.type == 'cpu' and t.shape == want.shape
+        ref = R.resample(torch.from_numpy(x).to(dtype).double().numpy(), up, down)
+        assert np.abs(t.double().numpy() - ref).max() <= tol * max(np.abs(ref).max(), 1.0), dtype
+    assert snd.resample(torch.zeros(211, dtype=torch.float64), *rates).shape == (R.out_len(211, up, down),)
+    assert snd.resample(torch.zeros(2, 0), *rates).shape == (2, 0) and snd.resample(np.zeros((2, 0), dtype=np.float32), *rates).shape == (2, 0)
+    assert snd.resample(torch.zeros(0, 5), *rates).shape == (0, R.out_len(5, up, down))
+
+
+def test_identity_ratio_returns_an_equal_copy(snd):
+    x = R.signal_rows(4, 2, 37)
+    got = snd.resample(x, 16000, 16000)
+    assert got is not x and got.dtype == np.float32 and np.array_equal(got, x) and not np.shares_memory(got, x)
+    t = torch.from_numpy(x)
+    for out in (snd.resample(t, 22050, 22050), _K().resample_poly(t, 3, 3)):
+        assert out is not t and torch.equal(out, t) and out.data_ptr() != t.data_ptr()
+
+
+def test_custom_taps_and_argument_errors(snd):
+    K = _K()
+    w = np.arange(1.0, 8.0)
+    x = torch.from_numpy(R.signal_rows(5, 2, 37)).double()
+    for up, down in ((2, 3), (3, 2)):
+        got = K.resample_poly(x, up, down, taps=w)
+        assert np.abs(got.numpy() - R.resample(x.numpy(), up, down, w * up)).max() <= 1e-12
+        assert np.abs(got.numpy() - signal.resample_poly(x.numpy(), up, down, axis=-1, window=w)).max() <= 1e-12
+        assert torch.equal(K.resample_poly(x, up, down, taps=list(w)), got)
+    assert torch.equal(K.resample_poly(x, 2, 1, taps=K.resample_taps(2, 1) / 2), K.resample_poly(x, 2, 1))
+    with pytest.raises(ValueError):
+        K.resample_poly(x, 2, 3, taps=np.ones(6))
+    with pytest.raises(ValueError):
+        K.resample_poly(x, 2, 3, taps=np.ones((3, 3)))
+    for up, down in ((0, 1), (1, 0), (-2, 3), (1.5, 2)):
+        with pytest.raises(ValueError):
+            K.resample_poly(x, up, down)
+    with pytest.raises(K.PsndError):
+        K.resample_poly(torch.zeros(()), 1, 2)
+    with pytest.raises(K.PsndError):
+        K.resample_poly(torch.zeros(2, 8, dtype=torch.int32), 1, 2)
+    with pytest.raises(K.PsndError):
+        snd.resample(np.float32(1.0), 2, 1)
+    with pytest.raises(ValueError):
+        snd.resample(x, 44100.0, 22050)
+
+
+@pytest.mark.parametrize('up,down', [(2, 1), (1, 2), (3, 2), (2, 3), (160, 147), (147, 320)])
+def test_cpu_autograd_is_the_adjoint(up, down):
+    K = _K()
+    g0 = torch.Generator().manual_seed(7)
+    x = torch.randn(2, 3, 211, dtype=torch.float64, generator=g0, requires_grad=True)
+    y = K.resample_poly(x, up, down)
+    g = torch.randn(y.shape, dtype=torch.float64, generator=g0)
+    (gx,) = torch.autograd.grad(y, x, g, create_graph=True)
+    assert gx.shape == x.shape
+    assert np.abs(gx.detach().numpy() - R.adjoint(g.numpy(), up, down, 211)).max() <= 1e-12
+    lhs, rhs = (y.detach() * g).sum().item(), (x.detach() * gx.detach()).sum().item()
+    assert abs(lhs - rhs) <= 1e-10 * max(abs(lhs), 1.0)                    # <resample(x), g> = <x, grad>
+    # second derivative: gx is linear in g, and the gradient of <gx, u> with respect to g is resample(u)
+    u = torch.randn(x.shape, dtype=torch.float64, generator=g0)
+    gg = g.clone().requires_grad_(True)
+    (gx2,) = torch.autograd.grad(K.resample_poly(x, up, down), x, gg, create_graph=True)
+    (d,) = torch.autograd.grad(gx2, gg, u)
+    assert np.abs(d.numpy() - R.resample(u.numpy(), up, down)).max() <= 1e-12
+
+
+def test_gradcheck_and_asymmetric_taps_on_the_cpu():
+    K = _K()
+    assert torch.autograd.gradcheck(lambda t: K.resample_poly(t, 3, 2), (torch.randn(1, 40, dtype=torch.float64, requires_grad=True),))
+    w = np.arange(1.0, 8.0)                                              # asymmetric: a missing or doubled flip shows
+    assert torch.autograd.gradcheck(lambda t: K.resample_poly(t, 2, 3, taps=w), (torch.randn(1, 23, dtype=torch.float64, requires_grad=True),))
+    x = torch.randn(2, 23, dtype=torch.float64, requires_grad=True)
+    y = K.resample_poly(x, 3, 2, taps=w)
+    g = torch.randn(y.shape, dtype=torch.float64)
+    (gx,) = torch.autograd.grad(y, x, g)
+    assert np.abs(gx.numpy() - R.adjoint(g.numpy(), 3, 2, 23, w * 3)).max() <= 1e-12
+
+
+# ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
+def test_abi_symbols_are_exported_declared_and_mirrored(L):
+    txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    h = ctypes.CDLL(L.LIB_PATH)
+    for name, ret, want in (('psnd_resample', 'int', ['x', 'N', 'T', 'h', 'taps', 'up', 'down', 'flip', 'y', 'T_out', 'stream']),
+                            ('psnd_resample_len', 'int64_t', ['T', 'up', 'down'])):
+        m = re.search(r'%s\s+%s\s*\((.*?)\)\s*;' % (ret, name), txt, flags=re.S)
+        assert m, 'include/psnd.h does not declare %s' % name
+        args = [s.strip() for s in m.group(1).split(',')]
+        assert [re.search(r'(\w+)$', s).group(1) for s in args] == want
+        assert hasattr(h, name)
+        res, argtypes = L.SIGNATURES[name]
+        assert res is (ctypes.c_int if ret == 'int' else ctypes.c_int64) and len(argtypes) == len(args)
+        for s, t in zip(args, argtypes):
+            kind = (ctypes.c_void_p if '*' in s else ctypes.c_int64 if s.startswith('int64_t') else ctypes.c_int)
+            assert t is kind, (s, t)
+    K = _K()
+    for macro, value in (('PSND_RESAMPLE_TILE', K.RESAMPLE_TILE), ('PSND_RESAMPLE_MAX_TAPS', K.RESAMPLE_MAX_TAPS)):
+        assert re.search(r'#define %s %d\b' % (macro, value), txt), macro
+    assert K.RESAMPLE_MAX_TAPS >= 12801 and K.RESAMPLE_TILE > 0
+    assert K.resample_taps(*K.resample_ratio(11025, 48000)).size == 12801 == K.resample_taps(*K.resample_ratio(16000, 11025)).size
+    assert L.lib().psnd_version() >= 145
+
+
+def test_resample_len(L):
+    lib = L.lib()
+    for up, down in ((1, 2), (2, 1), (3, 2), (320, 441), (441, 320)):
+        assert [lib.psnd_resample_len(t, up, down) for t in (-5, 0, 1, 7)] == [0, 0] + [-(-t * up // down) for t in (1, 7)]
+    assert lib.psnd_resample_len(1 << 40, 441, 320) == -(-(1 << 40) * 441 // 320)
+    assert lib.psnd_resample_len(7, 0, 2) == 0 and lib.psnd_resample_len(7, 2, -1) == 0
+
+
+def test_bad_arguments_are_refused_without_a_device(L):
+    lib = L.lib()
+    buf, buf2, hbuf = (ctypes.c_float * 64)(), (ctypes.c_float * 64)(), (ctypes.c_float * 64)()
+    x, y, h = (ctypes.cast(v, ctypes.c_void_p) for v in (buf, buf2, hbuf))
+
+    def call(x=None, N=1, T=16, h=None, taps=41, up=1, down=2, flip=0, y=None, T_out=8):
+        return lib.psnd_resample(x, N, T, h, taps, up, down, flip, y, T_out, None)
+
+    # every argument error with null buffers: refused before a pointer is looked at
+    assert call(taps=40) == -1 and b'taps' in lib.psnd_last_error()
+    assert call(taps=0) == -1 and call(taps=-3) == -1
+    assert call(taps=12803) == -1 and b'PSND_RESAMPLE_MAX_TAPS' in lib.psnd_last_error()
+    assert call(up=0) == -1 and call(up=-1) == -1 and call(down=0) == -1 and call(down=-7) == -1
+    assert call(N=-1) == -1 and call(T=-1) == -1 and call(T_out=-1) == -1
+    assert call(flip=2) == -1
+    assert call(x=x, y=x, h=h) == -1 and b'different' in lib.psnd_last_error()
+    assert call() == -1 and b'null' in lib.psnd_last_error()              # valid numbers, no buffers
+    assert call(x=x, y=y) == -1 and call(x=x, h=h) == -1 and call(y=y, h=h) == -1
+    assert call(x=x, y=y, h=h, N=1 << 31) == -2 and call(x=x, y=y, h=h, N=1 << 20, T_out=1 << 40) == -2
+    # nothing to do is fine and launches nothing - but the arguments are still checked
+    assert call(N=0) == 0 and call(T_out=0) == 0 and call(N=0, T=0, T_out=0) == 0
+    assert call(N=0, taps=4) == -1 and call(T_out=0, up=0) == -1 and call(N=0, x=x, y=x) == -1
+
+
+# ---- the module ---------------------------------------------------------------------------------------------------------------------------
+def test_resample_module():
+    from pytorch_sound.models.sound import Resample
+    K = _K()
+    m = Resample(22050, 16000)
+    assert (m.up, m.down) == (320, 441) and not list(m.parameters())
+    assert m.state_dict() == {} and [n for n, _ in m.named_buffers()] == ['taps']
+    assert m.taps.dtype == torch.float32 and np.array_equal(m.taps.numpy(), R.taps(320, 441).astype(np.float32))
+    x = torch.from_numpy(R.signal_rows(6, 2, 211))
+    y2, y3 = m(x), m(x.reshape(2, 1, 211))
+    n = R.out_len(211, 320, 441)
+    assert y2.shape == (2, n) and y3.shape == (2, 1, n) and torch.equal(y3[:, 0], y2)
+    assert torch.equal(y2, K.resample_poly(x, 320, 441))
+    assert m.to('meta').taps.device.type == 'meta'                       # the taps follow .to()
+    assert Resample(16000, 16000)(x).data_ptr() != x.data_ptr()
+    for bad in (torch.zeros(211), torch.zeros(2, 2, 211), torch.zeros(1, 1, 1, 8)):
+        with pytest.raises(RuntimeError):
+            Resample(2, 1)(bad)
+    with pytest.raises(ValueError):
+        Resample(22050.0, 16000)
