@@ -689,6 +689,42 @@ int64_t psnd_resample_len(int64_t T, int up, int down);
 int psnd_resample(const float *x, int64_t N, int64_t T, const float *h, int taps, int up, int down, int flip, float *y, int64_t T_out,
                   void *stream);
 
+/* ---- utils/silence.py: detect_silence (:25-80, pydub's detector on numpy: one x.dot(x) per window start in a Python loop) on device
+ *  tensors (psnd_silence.hip) ------------------------------------------------------------------------------------------------------------
+ *  Every row x of T_r samples (fp32) on its own; window L >= 1 samples, step s >= 1 samples (the reference's "ms" are sample counts).
+ *    Starts.    None if T_r < L; else 0, s, 2s, ... <= T_r - L, plus T_r - L itself when it is no multiple of s.
+ *    Decision.  The window at i is silent iff E(i) = sum_{t in [i, i+L)} x[t]^2 <= theta.  theta = L 10^(dB/10), formed in double on the
+ *               host and passed by value, so a call can be captured: the reference's rms <= 10^(dB/20).  dB = -inf gives theta = 0: only
+ *               windows of exact zeros are silent.  A window that holds a NaN or +-Inf sample is not silent (the reference: nan <= thr is
+ *               false), and such a sample changes the decision of no window that does not hold it.
+ *    Merging, in the order of silent starts, p = the silent start before: a silent start k opens a new range iff it is the first one, or
+ *               k != p + s and k > p + L.  A range is [first start, last start + L].  With s > L grid neighbours still merge across the gap
+ *               between them, as in the reference.
+ *    Outputs.   count[row] (int32); ranges[row][r][0:2] (int64) for r < count, -1 in the entries r >= count up to `cap`.
+ *               psnd_silence_cap(T, L) = floor((T - L) / (L + 1)) + 1 ranges per row always suffice (two range heads are more than L
+ *               apart); 0 for T < L.
+ *  E is exact to fp64 rounding of a sum of at most L + PSND_SILENCE_BLOCK terms - never a difference of two row-long prefix sums, which
+ *  loses a quiet window behind a loud passage.  Three launches, no workgroup waits on another inside one, no atomics:
+ *    A  per block of PSND_SILENCE_BLOCK samples of a row, the inclusive fp64 prefix of x^2 restarted at the block's first sample (the last
+ *       entry is the block's total) and the int32 prefix of the count of non-finite samples, which enter the fp64 sum as 0;
+ *    B  one lane per start: E = tail of the first block + the totals of the whole blocks between + head of the last block (three
+ *       non-negative parts), the non-finite count by the same decomposition, one byte per start;
+ *    C  one workgroup per row walks the flags in chunks: p is an exclusive prefix maximum of silent starts, range ordinals a prefix sum of
+ *       head flags (wave scans by ballots and one shuffle, the four waves meet through LDS, the previous silent start and the ordinal carried from chunk
+ *       to chunk); a head of ordinal r > 0 also writes the end of range r - 1, the last end is written behind the walk, then the -1 fill.
+ *  lengths : per-row valid lengths (device int64, clamped to [0, T]) or NULL for T everywhere - a zero-padded collated batch as ragged
+ *      rows; a row shorter than L has count 0.  scratch : psnd_silence_scratch_bytes(N, T, L, s) bytes, 16-byte aligned (12 per sample and
+ *      one per start, rounded up); every entry that is read has been written by the same call.  x may start on any 4-byte boundary.
+ *  PSND_E_ARG before anything is launched: L < 1, s < 1, cap < psnd_silence_cap(T, L), NaN theta, N or T < 0, a NULL pointer with
+ *  N, T > 0 (more than 2^31 - 1 workgroups: PSND_E_SHAPE).  N == 0 or T == 0: nothing to do.
+ *  psnd_silence_starts(T, L, s): the number of window starts of a row of T samples (host helper, as psnd_silence_cap). */
+#define PSND_SILENCE_BLOCK 1024
+int64_t psnd_silence_cap(int64_t T, int64_t L);
+int64_t psnd_silence_starts(int64_t T, int64_t L, int64_t s);
+size_t psnd_silence_scratch_bytes(int64_t N, int64_t T, int64_t L, int64_t s);
+int psnd_silence_ranges(const float *x, int64_t N, int64_t T, const int64_t *lengths, int64_t L, int64_t s, double theta, void *scratch,
+                        int32_t *count, int64_t *ranges, int64_t cap, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

@@ -139,6 +139,10 @@ SIGNATURES = {
     'psnd_lfilter': (_INT, [_P, _I64, _I64, _D, _D, _D, _D, _D, _INT, _INT, _P, _P, _P]),
     'psnd_resample_len': (_I64, [_I64, _INT, _INT]),
     'psnd_resample': (_INT, [_P, _I64, _I64, _P, _INT, _INT, _INT, _INT, _P, _I64, _P]),
+    'psnd_silence_cap': (_I64, [_I64, _I64]),
+    'psnd_silence_starts': (_I64, [_I64, _I64, _I64]),
+    'psnd_silence_scratch_bytes': (_c.c_size_t, [_I64, _I64, _I64, _I64]),
+    'psnd_silence_ranges': (_INT, [_P, _I64, _I64, _P, _I64, _I64, _D, _P, _P, _P, _I64, _P]),
     'psnd_stft_loss_blocks': (_I64, [_I64]),
     'psnd_stft_loss_partial': (_INT, [_P, _P, _I64, _I64, _F, _P, _P]),
     'psnd_stft_loss_final': (_INT, [_P, _P, _INT, _I64, _P, _P, _P]),

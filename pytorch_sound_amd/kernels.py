@@ -2,8 +2,8 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter` and `resample_poly` alone also take CPU tensors: there the
-scipy call IS the implementation or the definition; a HIP tensor never reaches it.)
+or a missing library raises.  (`lfilter`, `resample_poly` and `silence_ranges` alone also take CPU tensors: there the
+scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
 import os
@@ -1370,6 +1370,145 @@ def resample_poly(x, up, down, taps=None, device_taps=None):
             raise _lib.PsndError('resample: %d taps for the ratio %d / %d, the kernel holds at most RESAMPLE_MAX_TAPS = %d (no host path for '
                                  'a HIP tensor)' % (plan.h.size, up, down, RESAMPLE_MAX_TAPS))
     return ResampleFn.apply(x, up, down, plan, False, -(-x.shape[-1] * up // down), device_taps)
+
+
+SILENCE_BLOCK = 1024                                            # include/psnd.h
+
+
+def silence_theta(min_silence_len, silence_thresh):
+    """L 10^(dB/10) in float64: the bound on a window's energy that is the reference's rms <= 10^(dB/20).  -inf dB gives 0."""
+    db = float(silence_thresh)
+    if math.isnan(db):
+        raise ValueError('silence: silence_thresh is NaN')
+    try:
+        return float(min_silence_len) * 10.0 ** (db / 10.0)
+    except OverflowError:
+        return _INF
+
+
+def silence_cap(T, L):
+    """psnd_silence_cap: floor((T - L) / (L + 1)) + 1 ranges always suffice for a row of T samples, 0 for T < L"""
+    return 0 if L < 1 or T < L else (T - L) // (L + 1) + 1
+
+
+def silence_starts(T, L, s):
+    """psnd_silence_starts: the window starts 0, s, 2s, ... <= T - L and T - L itself"""
+    if T < L or T <= 0:
+        return np.zeros(0, dtype=np.int64)
+    i = np.arange(0, T - L + 1, s, dtype=np.int64)
+    return i if (T - L) % s == 0 else np.append(i, np.int64(T - L))
+
+
+def silence_energies(x, L, starts):
+    """(E, bad) of the windows [i, i + L) of one row, i in `starts`: the float64 energy with non-finite samples counted as 0, and the number
+    of non-finite samples.  The decomposition of psnd_silence.hip: prefix sums restarted every SILENCE_BLOCK samples, a window = tail of its
+    first block + whole blocks + head of its last block, so that a quiet window behind a loud passage keeps its digits."""
+    T, B = x.shape[0], SILENCE_BLOCK
+    if starts.size * L <= T:                                            # few windows (a wide step): each summed on its own, pairwise
+        w = np.asarray(x)[starts[:, None] + np.arange(L)].astype(np.float64)
+        fin = np.isfinite(w)
+        return (np.where(fin, w, 0.0) ** 2).sum(axis=1), (~fin).sum(axis=1)
+    x = np.asarray(x, dtype=np.float64)
+    fin = np.isfinite(x)
+    nb = -(-T // B)
+    sq = np.zeros(nb * B)
+    sq[:T] = np.where(fin, x, 0.0) ** 2
+    P = np.cumsum(sq.reshape(nb, B), axis=1).reshape(-1)                # inclusive, restarted per block
+    cnt = np.concatenate(([0], np.cumsum(~fin, dtype=np.int64)))       # integers: one row-long prefix is exact
+    e = starts + L - 1
+    b0, b1 = starts // B, e // B
+    before = np.where(starts % B == 0, 0.0, P[starts - 1])
+    same = b0 == b1
+    E = np.where(same, P[e] - before, P[b0 * B + B - 1] - before)
+    for k in range(1, L // B + 2):                                      # whole blocks between, first to last
+        b = b0 + k
+        E = E + np.where(b < b1, P[np.minimum(b, nb - 1) * B + B - 1], 0.0)
+    E = E + np.where(same, 0.0, P[e])
+    return E, cnt[starts + L] - cnt[starts]
+
+
+def silence_merge(k, L, s):
+    """silent starts `k` (ascending) -> (R, 2) ranges by the rule of include/psnd.h: k opens a range iff it is the first, or k != p + s and
+    k > p + L for the silent start p before it; a range is [first start, last start + L]"""
+    if k.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    head = np.ones(k.size, dtype=bool)
+    head[1:] = (k[1:] != k[:-1] + s) & (k[1:] > k[:-1] + L)
+    first = np.flatnonzero(head)
+    last = np.append(first[1:] - 1, k.size - 1)
+    return np.stack((k[first], k[last] + L), axis=1).astype(np.int64)
+
+
+def silence_ranges_host(x, L, s, theta):
+    """the definition on one row of numpy samples: (R, 2) int64"""
+    x = np.asarray(x).reshape(-1)
+    starts = silence_starts(x.shape[0], L, s)
+    if starts.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    E, bad = silence_energies(x, L, starts)
+    return silence_merge(starts[(bad == 0) & (E <= theta)], L, s)
+
+
+def silence_params(min_silence_len, seek_step):
+    for name, v in (('min_silence_len', min_silence_len), ('seek_step', seek_step)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('silence: %s=%r - a count of samples, at least 1' % (name, v))
+    return int(min_silence_len), int(seek_step)
+
+
+def silence_ranges(wav, min_silence_len, silence_thresh, seek_step=1, lengths=None):
+    """the silent ranges of every row of `wav` (..., T) by the definition of include/psnd.h (the reference's utils/silence.py detect_silence):
+    (count (N,) int32, ranges (N, cap, 2) int64) on wav's device, N = the product of the leading shape, cap = silence_cap(T, L); row n
+    has count[n] ranges [start, end], the entries behind them are -1.  `lengths`: per-row valid lengths (N,), clamped to [0, T].
+
+    HIP tensors run psnd_silence_ranges (float32; float16 / bfloat16 are cast; float64 raises) with no host synchronisation - the call can
+    be captured; `lengths` is then an int64 tensor on the same device (anything else is copied there).  CPU tensors go through the host
+    restatement above in float64.  No autograd: the outputs are integers."""
+    if not isinstance(wav, torch.Tensor):
+        raise _lib.PsndError('silence: a tensor is expected, got %s' % type(wav).__name__)
+    if wav.dim() == 0:
+        raise _lib.PsndError('silence: the input needs a time axis')
+    if not wav.is_floating_point():
+        raise _lib.PsndError('silence: floating input expected, got %s' % wav.dtype)
+    L, s = silence_params(min_silence_len, seek_step)
+    theta = silence_theta(L, silence_thresh)
+    T = wav.shape[-1]
+    N = math.prod(wav.shape[:-1])
+    cap = silence_cap(T, L)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths)
+        if lengths.is_floating_point() or lengths.numel() != N:
+            raise _lib.PsndError('silence: lengths must be %d integers, got %s %s' % (N, tuple(lengths.shape), lengths.dtype))
+    if not wav.is_cuda:
+        rows = wav.detach().reshape(N, T).to(torch.float64).numpy()
+        lens = [T] * N if lengths is None else [min(max(int(v), 0), T) for v in lengths.reshape(-1).tolist()]
+        count = np.zeros(N, dtype=np.int32)
+        ranges = np.full((N, cap, 2), -1, dtype=np.int64)
+        for n in range(N):
+            r = silence_ranges_host(rows[n, :lens[n]], L, s, theta)
+            count[n] = r.shape[0]
+            ranges[n, :r.shape[0]] = r
+        return torch.from_numpy(count), torch.from_numpy(ranges)
+    if wav.dtype == torch.float64:
+        raise _lib.PsndError('silence: no float64 instance on HIP tensors (a round trip through float32 would silently change which windows '
+                             'pass the threshold): pass a float32 tensor, or a CPU tensor in float64')
+    if wav.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.PsndError('silence: floating input expected, got %s' % wav.dtype)
+    xf = wav.detach().reshape(N, T).float()
+    if N * T > 0 and (xf.stride(-1) != 1 or (N > 1 and xf.stride(0) != T)):
+        xf = xf.contiguous()
+    if lengths is not None:
+        lengths = lengths.reshape(-1).to(device=wav.device, dtype=torch.int64).contiguous()
+    if N * T == 0:                                       # nothing to launch: rows without samples have no ranges
+        return torch.zeros(N, dtype=torch.int32, device=wav.device), torch.empty((N, 0, 2), dtype=torch.int64, device=wav.device)
+    count = torch.empty(N, dtype=torch.int32, device=wav.device)
+    ranges = torch.empty((N, cap, 2), dtype=torch.int64, device=wav.device)
+    nbytes = int(lib().psnd_silence_scratch_bytes(N, T, L, s))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=wav.device) if nbytes else None
+    with torch.cuda.device(wav.device):
+        check(lib().psnd_silence_ranges(ptr(xf), N, T, ptr(lengths), L, s, theta, ptr(scratch), ptr(count), ptr(ranges), cap,
+                                        stream_ptr(wav.device)), 'psnd_silence_ranges')
+    return count, ranges
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):
