@@ -1,188 +1,17 @@
-"""ctypes binding of libpsnd_hip.so (include/psnd.h).  The product path has NO fallback:
-if the library is missing or a call fails, an exception is raised."""
+"""ctypes binding of libpsnd_hip.so.  include/psnd.h is the only place an entry point, a descriptor struct or a constant is declared: this
+module reads it once at import and derives SIGNATURES, LAB_SIGNATURES, the ctypes structs and DEFINES from it (parse_header).  A header
+it cannot type completely does not load.  The product path has NO fallback: if the library is missing or a call fails, an exception is
+raised."""
 import ctypes
 import os
+import re
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PSND_LIB', os.path.join(_HERE, 'libpsnd_hip.so'))   # PSND_LIB: A/B builds of the same ABI
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'psnd.h')
 
-PSND_OK = 0
-FRAMING_CENTER = 0
-FRAMING_HIFIGAN = 1
-FRAMING_NONE = 2
-LOG_NONE, LOG_E, LOG_10 = 0, 1, 2
-MASK_NONE, MASK_LINEAR, MASK_SIGMOID = 0, 1, 2
-
-_c = ctypes
-_P = _c.c_void_p
-_I64 = _c.c_int64
-_INT = _c.c_int
-_F = _c.c_float
-_D = _c.c_double
-_U32 = _c.c_uint32
-_U64 = _c.c_uint64
-
-# name -> (restype, argtypes); mirrors include/psnd.h one to one
-SIGNATURES = {
-    'psnd_version': (_INT, []),
-    'psnd_last_error': (_c.c_char_p, []),
-    'psnd_event_create': (_P, []),
-    'psnd_event_destroy': (_INT, [_P]),
-    'psnd_event_record_external': (_INT, [_P, _P]),
-    'psnd_stream_wait_event': (_INT, [_P, _P]),
-    'psnd_event_external_supported': (_INT, []),
-    'psnd_frame_count': (_I64, [_I64, _INT, _INT, _INT]),
-    'psnd_frame_sample_index': (_I64, [_I64, _INT, _I64, _INT, _INT, _INT]),
-    'psnd_stft_plan_bytes': (_c.c_size_t, [_INT]),
-    'psnd_stft_plan_build': (_INT, [_INT, _P, _P]),
-    'psnd_stft_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P, _P, _P, _P]),
-    'psnd_stft_mag_nfk': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P]),
-    'psnd_stft_bwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P, _P, _P, _P]),
-    'psnd_istft': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _F, _P, _P]),
-    'psnd_stft_mr_plan_bytes': (_c.c_size_t, [_INT]),
-    'psnd_stft_mr_plan_build': (_INT, [_INT, _P, _P]),
-    'psnd_stft_mr_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _c.c_size_t, _F, _P, _P, _P, _P, _P]),
-    'psnd_stft_mr_bwd_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT, _INT, _INT]),
-    'psnd_stft_mr_bwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _c.c_size_t, _F, _P, _P, _P, _P, _c.c_size_t, _P, _P]),
-    'psnd_istft_mr_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT]),
-    'psnd_istft_mr': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P]),
-    'psnd_istft_reim': (_INT, [_P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _F, _P, _P]),
-    'psnd_istft_reim_mr': (_INT, [_P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P]),
-    'psnd_istft_reim_bwd_scratch_bytes': (_c.c_size_t, [_I64, _I64, _INT]),
-    'psnd_istft_reim_bwd': (_INT, [_P, _P, _P, _P, _INT, _I64, _I64, _INT, _INT, _P, _c.c_size_t, _F, _P, _c.c_size_t, _P, _P, _P, _P]),
-    'psnd_mel_plan_bytes': (_c.c_size_t, [_INT, _INT]),
-    'psnd_mel_plan_build': (_INT, [_INT, _INT, _P, _P]),
-    'psnd_mel_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P]),
-    'psnd_mel_bwd': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P]),
-    'psnd_logmel_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _INT, _P, _INT, _F, _F, _F, _F, _P, _P]),
-    'psnd_conv1d_cl': (_INT, [_P, _P, _P, _F, _P, _P, _P, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _F, _F, _P, _P, _P, _P]),
-    'psnd_conv1d_cl_pair_supported': (_INT, [_INT, _INT, _INT, _INT, _INT, _INT]),
-    'psnd_conv1d_cl_pair': (_INT, [_P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _F, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _F, _P, _P, _P]),
-    'psnd_conv1d_cl_wgrad': (_INT, [_P, _P, _P, _F, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_conv1d_prep': (_INT, [_P, _P, _P, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_conv1d_wnorm_bwd': (_INT, [_P, _P, _INT, _P, _P, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_conv1d_cl_bwd': (_INT, [_P, _P, _P, _F, _P, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _F, _P, _P, _P, _P]),
-    'psnd_conv1d_cl_wgrad_multi_splits': (_INT, [_I64, _INT, _INT, _INT, _INT, _INT]),
-    'psnd_conv1d_cl_wgrad_multi': (_INT, [_P, _INT, _I64, _INT, _P]),
-    'psnd_nan_flag': (_INT, [_P, _I64, _P, _P]),
-    'psnd_conv1d_cl_chain_rows': (_INT, [_INT, _INT, _INT, _P]),
-    'psnd_conv1d_cl_chain_plan': (_INT, [_INT, _INT, _INT, _P, _I64, _P]),
-    'psnd_conv1d_cl_chain': (_INT, [_P, _P, _P, _INT, _I64, _INT, _INT, _INT, _INT, _INT, _P]),
-    'psnd_conv_chain_stats': (None, [_P]),
-    'psnd_conv1d_cl_pair_bwd_supported': (_INT, [_INT, _INT, _INT, _INT, _INT, _INT]),
-    'psnd_conv1d_cl_pair_bwd_splits': (_INT, [_I64, _INT, _INT, _INT]),
-    'psnd_conv1d_cl_pair_bwd': (_INT, [_P, _P, _P, _F, _P, _P, _P, _F, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P,
-                                       _P, _P, _INT, _INT, _P, _P, _P]),
-    'psnd_conv1d_wnorm_bwd_multi': (_INT, [_P, _INT, _P]),
-    'psnd_conv1d_prep_multi': (_INT, [_P, _INT, _INT, _INT, _INT, _P]),
-    'psnd_conv1d_cl_wgrad_splits': (_INT, [_I64, _INT, _INT, _INT, _INT]),
-    'psnd_mask_head_l1_blocks': (_I64, [_I64, _I64, _INT]),
-    'psnd_masked_l1_blocks': (_I64, [_I64]),
-    'psnd_masked_l1_fwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _P, _P, _P, _P]),
-    'psnd_masked_l1_bwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _P, _P, _P, _P, _P]),
-    'psnd_to_cl_nfk': (_INT, [_P, _I64, _INT, _I64, _INT, _INT, _INT, _INT, _P, _P]),
-    'psnd_mask_head_l1_blocks_nfk': (_I64, [_I64, _I64, _INT]),
-    'psnd_mask_head_l1_fwd_nfk': (_INT, [_P, _P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P, _P]),
-    'psnd_mask_head_l1_bwd_nfk': (_INT, [_P, _P, _P, _P, _P, _P, _F, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_mel_fwd_nfk': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P]),
-    'psnd_mel_bwd_nfk': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P]),
-    'psnd_mel_l1_fwd_nfk': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P, _P]),
-    'psnd_mel_l1_bwd_nfk': (_INT, [_P, _P, _P, _F, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P]),
-    'psnd_mask_head_l1_fwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P, _P]),
-    'psnd_mask_head_l1_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _F, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_mel_l1_blocks': (_I64, [_I64, _I64, _INT]),
-    'psnd_mel_l1_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P, _P, _P]),
-    'psnd_mel_l1_bwd': (_INT, [_P, _P, _P, _F, _I64, _I64, _INT, _INT, _P, _INT, _F, _F, _F, _F, _P, _P]),
-    'psnd_l1_loss_combine': (_INT, [_P, _P, _P, _INT, _P, _P, _P]),
-    'psnd_conv_stats': (_INT, [_P, _INT]),
-    'psnd_conv_pair_stats': (_INT, [_P, _INT]),
-    'psnd_convtr1d_prep_multi': (_INT, [_P, _INT, _INT, _P]),
-    'psnd_convtr1d_prep': (_INT, [_P, _P, _P, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_convtr1d_cl_fwd': (_INT, [_P, _P, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _F, _P, _P, _P]),
-    'psnd_convtr1d_cl_wgrad_splits': (_INT, [_I64, _INT, _INT, _INT, _INT]),
-    'psnd_convtr1d_cl_bwd': (_INT, [_P, _P, _P, _F, _P, _P, _I64, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_convtr1d_wnorm_bwd': (_INT, [_P, _INT, _P, _P, _INT, _INT, _INT, _INT, _INT, _INT, _P, _P, _P]),
-    'psnd_cl_mean_act_fwd': (_INT, [_P, _P, _P, _P, _INT, _F, _P, _I64, _P]),
-    'psnd_cl_mean_act_bwd': (_INT, [_P, _P, _INT, _F, _P, _I64, _P]),
-    'psnd_cl_sum2': (_INT, [_P, _INT, _P, _P, _INT, _P, _I64, _P]),
-    'psnd_grad_pack_bf16': (_INT, [_P, _P, _I64, _F, _P]),
-    'psnd_grad_unpack_bf16': (_INT, [_P, _P, _I64, _F, _P]),
-    'psnd_cl_colsum_splits': (_INT, [_I64, _INT]),
-    'psnd_cl_colsum': (_INT, [_P, _I64, _INT, _INT, _INT, _INT, _P, _P, _P]),
-    'psnd_posenc': (_INT, [_P, _P, _F, _I64, _INT, _I64, _I64, _P, _P]),
-    'psnd_groupnorm1_fwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _F, _INT, _P, _P, _P, _P]),
-    'psnd_groupnorm1_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _I64, _INT, _I64, _INT, _P, _P, _P, _P, _P]),
-    'psnd_groupnorm1_drop_fwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _F, _INT, _P, _P, _P, _P, _U32, _F, _P]),
-    'psnd_groupnorm1_drop_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _I64, _INT, _I64, _INT, _P, _P, _P, _P, _P, _P, _U32, _F, _P]),
-    'psnd_rng_seed': (_INT, [_P, _U64, _U64, _P]),
-    'psnd_rng_next': (_INT, [_P, _P, _P]),
-    'psnd_linear1x1_fwd': (_INT, [_P, _P, _P, _I64, _INT, _INT, _I64, _INT, _INT, _P, _P]),
-    'psnd_linear1x1_wgrad_slabs': (_I64, [_I64, _INT, _INT, _I64]),
-    'psnd_linear1x1_bwd': (_INT, [_P, _P, _P, _P, _I64, _INT, _INT, _I64, _INT, _P, _P, _P, _P, _P]),
-    'psnd_linear1x1_bwd_acc': (_INT, [_P, _P, _P, _P, _I64, _INT, _INT, _I64, _INT, _P, _P, _P, _P, _P, _P]),
-    'psnd_linear1x1_bwd_ex': (_INT, [_P, _P, _P, _P, _I64, _INT, _INT, _I64, _INT, _INT, _I64, _P, _P, _P, _P, _P, _P, _P]),
-    'psnd_linear1x1_fwd_ex': (_INT, [_P, _P, _P, _I64, _INT, _INT, _I64, _INT, _INT, _INT, _I64, _P, _P]),
-    'psnd_mha_fwd': (_INT, [_P, _P, _I64, _INT, _INT, _I64, _P, _P, _P, _INT, _P]),
-    'psnd_mha_bwd': (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _INT, _INT, _I64, _P, _P, _INT, _P]),
-    'psnd_mha_bwd_parts': (_INT, [_P, _P, _P, _P, _P, _P, _P, _I64, _INT, _INT, _I64, _P, _P, _INT, _INT, _P]),
-    'psnd_softmax_keys_fwd': (_INT, [_P, _P, _I64, _I64, _F, _P]),
-    'psnd_softmax_keys_bwd': (_INT, [_P, _P, _I64, _I64, _F, _P, _P]),
-    'psnd_polar_bwd': (_INT, [_P, _P, _P, _P, _I64, _P, _P, _P]),
-    'psnd_preemphasis_fwd': (_INT, [_P, _I64, _I64, _F, _P, _P]),
-    'psnd_preemphasis_bwd': (_INT, [_P, _I64, _I64, _F, _P, _P]),
-    'psnd_ipreemph_fwd': (_INT, [_P, _I64, _I64, _P, _P, _INT, _P, _P]),
-    'psnd_ipreemph_bwd': (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _INT, _P, _P, _P, _P]),
-    'psnd_volnorm_fwd': (_INT, [_P, _I64, _I64, _INT, _INT, _F, _P, _I64, _P, _P]),
-    'psnd_volnorm_reverse': (_INT, [_P, _I64, _I64, _INT, _INT, _F, _P, _P, _I64, _P]),
-    'psnd_lfilter_spans': (_I64, [_I64]),
-    'psnd_lfilter': (_INT, [_P, _I64, _I64, _D, _D, _D, _D, _D, _INT, _INT, _P, _P, _P]),
-    'psnd_resample_len': (_I64, [_I64, _INT, _INT]),
-    'psnd_resample': (_INT, [_P, _I64, _I64, _P, _INT, _INT, _INT, _INT, _P, _I64, _P]),
-    'psnd_silence_cap': (_I64, [_I64, _I64]),
-    'psnd_silence_starts': (_I64, [_I64, _I64, _I64]),
-    'psnd_silence_scratch_bytes': (_c.c_size_t, [_I64, _I64, _I64, _I64]),
-    'psnd_silence_ranges': (_INT, [_P, _I64, _I64, _P, _I64, _I64, _D, _P, _P, _P, _I64, _P]),
-    'psnd_stft_loss_blocks': (_I64, [_I64]),
-    'psnd_stft_loss_partial': (_INT, [_P, _P, _I64, _I64, _F, _P, _P]),
-    'psnd_stft_loss_final': (_INT, [_P, _P, _INT, _I64, _P, _P, _P]),
-    'psnd_stft_loss_bwd': (_INT, [_P, _P, _I64, _I64, _F, _P, _P, _INT, _P, _P, _P]),
-    'psnd_stft_bwd_msl_supported': (_INT, [_INT, _INT]),
-    'psnd_stft_fwd_msl_blocks': (_I64, [_I64, _INT, _INT]),
-    'psnd_stft_fwd_msl': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _F, _P, _F, _P, _P]),
-    'psnd_stft_loss_final_blocks': (_INT, [_P, _P, _P, _INT, _I64, _P, _P, _P]),
-    'psnd_stft_bwd_msl': (_INT, [_P, _I64, _I64, _INT, _INT, _INT, _P, _F, _P, _P, _P, _INT, _F, _INT, _P, _P]),
-    'psnd_frame_mask_frames': (_I64, [_I64, _INT, _INT]),
-    'psnd_frame_mask': (_INT, [_P, _I64, _I64, _INT, _INT, _P, _P]),
-    'psnd_pad_collate': (_INT, [_P, _P, _P, _I64, _I64, _P, _P, _P]),
-    'psnd_im2col_f32': (_INT, [_P, _I64, _INT, _I64, _INT, _INT, _INT, _INT, _INT, _I64, _F, _P, _P]),
-    'psnd_col2im_f32': (_INT, [_P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _INT, _INT, _I64, _F, _P, _P]),
-    'psnd_adam_chunk': (_I64, []),
-    'psnd_adam_table_bytes': (_I64, []),
-    'psnd_adam_step': (_INT, [_P, _INT, _P, _P, _I64, _D, _D, _D, _D, _D, _INT, _P, _P, _P, _F, _P, _P]),
-    'psnd_adam_step_logged': (_INT, [_P, _INT, _P, _P, _I64, _D, _D, _D, _D, _D, _INT, _P, _P, _P, _F, _P, _P, _INT, _INT, _P]),
-    'psnd_adam_step_sched': (_INT, [_P, _INT, _P, _P, _I64, _D, _D, _D, _D, _INT, _P, _P, _P, _F, _P, _P, _INT, _INT, _P, _INT, _INT, _INT, _P, _INT, _P]),
-    'psnd_grad_sumsq': (_INT, [_P, _INT, _P, _P, _I64, _F, _P, _INT, _F, _P, _P, _P, _P]),
-    'psnd_mask_head_fwd': (_INT, [_P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_mask_head_bwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_pqmf_analysis': (_INT, [_P, _P, _I64, _I64, _INT, _INT, _INT, _F, _P, _P]),
-    'psnd_pqmf_synthesis': (_INT, [_P, _P, _I64, _I64, _I64, _INT, _INT, _INT, _F, _P, _P]),
-    'psnd_lstft_analysis': (_INT, [_P, _P, _P, _I64, _I64, _INT, _INT, _INT, _P, _P, _P, _P]),
-    'psnd_lstft_mag_bwd': (_INT, [_P, _P, _P, _I64, _INT, _I64, _P, _P]),
-    'psnd_lstft_synthesis': (_INT, [_P, _P, _P, _P, _I64, _INT, _I64, _INT, _INT, _I64, _P, _P]),
-    'psnd_lstft_wgrad_slabs': (_I64, [_I64, _INT, _INT, _I64]),
-    'psnd_lstft_basis_grad': (_INT, [_P, _P, _P, _I64, _I64, _INT, _INT, _INT, _I64, _P, _P, _P]),
-    'psnd_l1_loss_blocks': (_I64, [_I64]),
-    'psnd_l1_loss_fwd': (_INT, [_P, _P, _I64, _P, _P, _P]),
-    'psnd_l1_loss_bwd': (_INT, [_P, _P, _I64, _P, _P, _P, _P]),
-    'psnd_l1_loss_sum_fwd': (_INT, [_P, _P, _P, _P, _INT, _P, _P, _P]),
-    'psnd_l1_loss_bwd_w': (_INT, [_P, _P, _I64, _P, _D, _P, _P, _P]),
-    'psnd_to_cl': (_INT, [_P, _I64, _INT, _I64, _INT, _INT, _INT, _INT, _P, _P]),
-    'psnd_from_cl': (_INT, [_P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_from_cl_tanh': (_INT, [_P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-    'psnd_to_cl_tanh_bwd': (_INT, [_P, _P, _I64, _INT, _I64, _INT, _INT, _INT, _P, _P]),
-}
-
+_P = ctypes.c_void_p
 _lib = None
 
 
@@ -190,23 +19,97 @@ class PsndError(RuntimeError):
     pass
 
 
-class WgradDesc(ctypes.Structure):
-    """psnd_wgrad_desc of include/psnd.h"""
-    _fields_ = [('g', _P), ('xa', _P), ('gw_part', _P), ('gbias_part', _P), ('off0', _INT), ('dstep', _INT),
-                ('Ca', _INT), ('Cb', _INT), ('k', _INT), ('splits', _INT)]
+# ---- the header's grammar: anything with a `*` is a pointer, these are the scalars and the return types -----------------------------------
+_SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t,
+            'uint32_t': ctypes.c_uint32, 'uint64_t': ctypes.c_uint64}
+_RETURNS = {'void': None, 'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'void *': _P,
+            'const char *': ctypes.c_char_p}
 
 
-class ChainPair(ctypes.Structure):
-    """psnd_chain_pair of include/psnd.h"""
-    _fields_ = [('W1', _P), ('bias1', _P), ('act1_slope', _F), ('mid_out', _P), ('W2', _P), ('bias2', _P),
-                ('off1', _INT), ('dstep1', _INT), ('off2', _INT), ('dstep2', _INT), ('act2_slope', _F), ('out_raw', _P), ('out_act', _P),
-                ('M1', _P), ('M2', _P), ('m1_slope', _F), ('m2_slope', _F)]
+def _scalar(words, decl):
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise PsndError('include/psnd.h: type `%s` of `%s` is outside the binding\'s grammar' % (' '.join(words), decl))
+    return _SCALARS[words[0]]
 
 
-class WnormDesc(ctypes.Structure):
-    """psnd_wnorm_desc of include/psnd.h"""
-    _fields_ = [('gw_part', _P), ('gbias_part', _P), ('v', _P), ('g', _P), ('gv', _P), ('gg', _P), ('gbias', _P),
-                ('splits', _INT), ('Cout', _INT), ('Cin', _INT), ('k', _INT), ('Cb', _INT), ('Ca', _INT)]
+def _prototypes(text):
+    """`ret psnd_name(args);` declarations and nothing else -> {name: (restype, [argtypes])}"""
+    *decls, tail = text.split(';')
+    if tail.strip():
+        raise PsndError('include/psnd.h: `%s` is not closed by a `;`' % ' '.join(tail.split()))
+    out = {}
+    for decl in (' '.join(d.split()) for d in decls if d.strip()):
+        m = re.fullmatch(r'([^()]*?)\b(psnd_\w+) ?\(([^()]*)\)', decl)
+        ret = m and re.sub(r' ?\* ?', ' *', m.group(1)).strip()
+        if not m or ret not in _RETURNS or m.group(2) in out:
+            raise PsndError('include/psnd.h: cannot read `%s` as one prototype of a known return type' % decl)
+        args = [] if m.group(3).strip() == 'void' else [a.strip() for a in m.group(3).split(',')]
+        out[m.group(2)] = (_RETURNS[ret], [_P if '*' in a else _scalar(a.split()[:-1], decl) for a in args])
+    return out
+
+
+def _fields(name, body):
+    """the body of `typedef struct name { ... } name;` -> [(field, ctype)], declarators such as `const void *g, *xa;` split"""
+    out = []
+    for decl in (' '.join(d.split()) for d in body.split(';') if d.strip()):
+        first, *more = [p.strip() for p in decl.split(',')]
+        base = first.replace('*', ' ').split()[:-1]
+        for p in [first] + more:
+            field = re.search(r'\w+$', p)
+            if not field:
+                raise PsndError('include/psnd.h: cannot read field `%s` of %s' % (decl, name))
+            out.append((field.group(0), _P if '*' in p else _scalar(base, '%s: %s' % (name, decl))))
+    return out
+
+
+def parse_header(text):
+    """the text of include/psnd.h -> (signatures, lab signatures, {struct: [(field, ctype)]}, {macro: int}); raises PsndError on anything
+    outside the grammar instead of skipping it"""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    defines = {}
+    for name, params, body in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)([^\n]*)', text, flags=re.M):
+        m = re.fullmatch(r'(-?\d+)|\(\s*(-?\d+)\s*\)', body.strip())
+        if m:
+            defines[name] = int(m.group(1) or m.group(2))
+        elif not params and body.strip():             # the include guard has no body; function-like macros are left to C
+            raise PsndError('include/psnd.h: `#define %s %s` is not an integer literal' % (name, body.strip()))
+    text = re.sub(r'#ifdef __cplusplus.*?#endif', ' ', text, flags=re.S)
+    lab = ' '.join(re.findall(r'#ifdef PSND_LAB\b(.*?)#endif', text, flags=re.S))
+    text = re.sub(r'#ifdef PSND_LAB\b.*?#endif', ' ', text, flags=re.S)
+    for line in re.findall(r'^[ \t]*#[^\n]*', text, flags=re.M):
+        if not re.match(r'\s*#\s*(include|define|ifndef PSND_H|endif)\b', line):
+            raise PsndError('include/psnd.h: `%s`: conditional blocks other than PSND_LAB are outside the binding\'s grammar' % line.strip())
+    text = re.sub(r'^[ \t]*#[^\n]*', ' ', text, flags=re.M)
+    struct = r'typedef struct (psnd_\w+) \{(.*?)\} \1;'
+    structs = {name: _fields(name, body) for name, body in re.findall(struct, text, flags=re.S)}
+    return _prototypes(re.sub(struct, ' ', text, flags=re.S)), _prototypes(lab), structs, defines
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise PsndError('include/psnd.h not found at %s (%s): the binding is derived from it' % (HEADER_PATH, e))
+
+
+# name -> (restype, argtypes) of every entry point / of those of a -DPSND_LAB build only; struct -> fields; PSND_* macro -> value
+SIGNATURES, LAB_SIGNATURES, _STRUCTS, DEFINES = _read_header()
+
+
+def _struct(name):
+    return type(''.join(w.capitalize() for w in name.split('_')[1:]), (ctypes.Structure,),
+                {'_fields_': _STRUCTS[name], '__doc__': '%s of include/psnd.h' % name})
+
+
+WgradDesc = _struct('psnd_wgrad_desc')
+ChainPair = _struct('psnd_chain_pair')
+WnormDesc = _struct('psnd_wnorm_desc')
+
+PSND_OK = DEFINES['PSND_OK']
+FRAMING_CENTER, FRAMING_HIFIGAN, FRAMING_NONE = (DEFINES['PSND_FRAMING_' + n] for n in ('CENTER', 'HIFIGAN', 'NONE'))
+LOG_NONE, LOG_E, LOG_10 = (DEFINES['PSND_LOG_' + n] for n in ('NONE', 'E', '10'))
+MASK_NONE, MASK_LINEAR, MASK_SIGMOID = (DEFINES['PSND_MASK_' + n] for n in ('NONE', 'LINEAR', 'SIGMOID'))
 
 
 def lib():
@@ -239,7 +142,6 @@ def _load(path):
 
 
 LAB_LIB_PATH = os.path.join(_HERE, 'libpsnd_hip_lab.so')     # `python -m pytorch_sound_amd._build --lab`
-LAB_SIGNATURES = {'psnd_env_refresh': (None, [])}
 
 
 def is_lab() -> bool:

@@ -1334,7 +1334,8 @@ class ResBlockCL(torch.autograd.Function):
             handed = set()
 
             def wgrad_batch(part):
-                """the weight gradients of these convs (wbatch entries) as psnd_conv1d_cl_wgrad_multi launches of <= 32"""
+                """the weight gradients of these convs (wbatch entries) as psnd_conv1d_cl_wgrad_multi launches of <= 32: the header's
+                `n (<= 32)` of that entry point (WGRAD_MULTI_MAX of csrc/psnd_conv.hip), which has no macro - not PSND_WNORM_MAX"""
                 for j0 in range(0, len(part), 32):
                     sub = part[j0:j0 + 32]
                     # row ranges: what suits the most frequent shape of the launch (the body's 256 -> 256 convs); the others take the same
@@ -1355,8 +1356,8 @@ class ResBlockCL(torch.autograd.Function):
                 """weight-norm backward of these convs (their slabs are complete on this stream), then the hand-over of what went straight
                 into the sink's buffers"""
                 ds = [descs[ci] for ci in convs]
-                for j0 in range(0, len(ds), 32):                 # PSND_WNORM_MAX descriptors per launch
-                    chunk = ds[j0:j0 + 32]
+                for j0 in range(0, len(ds), _lib.DEFINES['PSND_WNORM_MAX']):
+                    chunk = ds[j0:j0 + _lib.DEFINES['PSND_WNORM_MAX']]
                     arr = (_lib.WnormDesc * len(chunk))(*chunk)
                     check(lib().psnd_conv1d_wnorm_bwd_multi(ctypes.addressof(arr), len(chunk), st), 'psnd_conv1d_wnorm_bwd_multi')
                 out = []

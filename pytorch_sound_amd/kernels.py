@@ -1081,7 +1081,7 @@ class PreEmphasisFn(torch.autograd.Function):
         return gx, None
 
 
-IPREEMPH_SPAN, IPREEMPH_WARM_MAX, IPREEMPH_SEQ, IPREEMPH_AUTO = 8192, 2048, -1, -2        # include/psnd.h
+IPREEMPH_SPAN, IPREEMPH_WARM_MAX, IPREEMPH_SEQ, IPREEMPH_AUTO = (_lib.DEFINES['PSND_IPREEMPH_' + n] for n in ('SPAN', 'WARM_MAX', 'SEQ', 'AUTO'))
 
 
 class InversePreEmphasisFn(torch.autograd.Function):
@@ -1123,7 +1123,7 @@ class InversePreEmphasisFn(torch.autograd.Function):
         return (gx if need[0] else None, gw[0].reshape(w_ih.shape) if need[1] else None, gw[1].reshape(w_hh.shape) if need[2] else None, None)
 
 
-LFILTER_SPAN, LFILTER_PARALLEL, LFILTER_SEQ = 8192, 0, 1        # include/psnd.h
+LFILTER_SPAN, LFILTER_PARALLEL, LFILTER_SEQ = (_lib.DEFINES['PSND_LFILTER_' + n] for n in ('SPAN', 'PARALLEL', 'SEQ'))
 
 
 def lfilter_section(b, a):
@@ -1211,7 +1211,7 @@ def lfilter(x, b, a, reverse=False, instance=None):
     return LFilterFn.apply(x, sec, bool(reverse), instance)
 
 
-RESAMPLE_TILE, RESAMPLE_MAX_TAPS = 1024, 12801                  # include/psnd.h
+RESAMPLE_TILE, RESAMPLE_MAX_TAPS = _lib.DEFINES['PSND_RESAMPLE_TILE'], _lib.DEFINES['PSND_RESAMPLE_MAX_TAPS']
 
 
 def resample_ratio(orig_sr, new_sr):
@@ -1372,7 +1372,7 @@ def resample_poly(x, up, down, taps=None, device_taps=None):
     return ResampleFn.apply(x, up, down, plan, False, -(-x.shape[-1] * up // down), device_taps)
 
 
-SILENCE_BLOCK = 1024                                            # include/psnd.h
+SILENCE_BLOCK = _lib.DEFINES['PSND_SILENCE_BLOCK']
 
 
 def silence_theta(min_silence_len, silence_thresh):

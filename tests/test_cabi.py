@@ -10,11 +10,33 @@ from conftest import ROOT
 from oracle import features as ofe
 
 
-def _declared():
+CTYPE = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t,
+         'uint32_t': ctypes.c_uint32, 'uint64_t': ctypes.c_uint64}
+
+
+def _header_text(lab=False):
+    """include/psnd.h without comments: the product's declarations, or (lab) the inside of the #ifdef PSND_LAB blocks"""
     txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
     txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    txt = re.sub(r'#ifdef PSND_LAB.*?#endif', '', txt, flags=re.S)         # lab-only entry points (libpsnd_hip_lab.so)
-    return sorted(set(re.findall(r'\b(psnd_[a-z0-9_]+)\s*\(', txt)))
+    if lab:
+        return '\n'.join(re.findall(r'#ifdef PSND_LAB(.*?)#endif', txt, flags=re.S))         # lab-only entry points (libpsnd_hip_lab.so)
+    return re.sub(r'#ifdef PSND_LAB.*?#endif', '', txt, flags=re.S)
+
+
+def _declared(lab=False):
+    return sorted(set(re.findall(r'\b(psnd_[a-z0-9_]+)\s*\(', _header_text(lab))))
+
+
+def _prototypes(txt):
+    """this file's own reader of the header (nothing of the package's parser): name -> (restype, [argtypes], [argument texts])"""
+    out = {}
+    txt = re.sub(r'^[ \t]*#.*$', '', txt, flags=re.M)
+    for ret, name, arglist in re.findall(r'(\w[\w\s]*?[\s*]+)(psnd_\w+)\s*\(([^()]*)\)\s*;', txt):
+        args = [] if arglist.strip() == 'void' else [' '.join(a.split()) for a in arglist.split(',')]
+        res = ((ctypes.c_char_p if 'char' in ret else ctypes.c_void_p) if '*' in ret else
+               None if ret.strip() == 'void' else CTYPE[ret.strip()])
+        out[name] = (res, [ctypes.c_void_p if '*' in a else CTYPE[a.split()[0]] for a in args], args)
+    return out
 
 
 @pytest.fixture(scope='module')
@@ -36,15 +58,90 @@ def test_exports_every_declared_symbol(L):
     assert L.lib().psnd_version() >= 100
 
 
+def test_every_signature_matches_the_header(L):
+    """return type, arity and every argument type of every declared function, the lab block included, against the binding's tables"""
+    for lab, table in ((False, L.SIGNATURES), (True, L.LAB_SIGNATURES)):
+        protos = _prototypes(_header_text(lab))
+        assert sorted(protos) == _declared(lab) == sorted(table), 'ctypes table and header disagree'
+        for name, (res, argtypes, args) in protos.items():
+            assert table[name][0] is res, '%s: return type %s' % (name, table[name][0])
+            assert len(table[name][1]) == len(args), '%s: %d arguments bound, %d declared' % (name, len(table[name][1]), len(args))
+            for a, want, got in zip(args, argtypes, table[name][1]):
+                assert got is want, '%s: `%s` is bound as %s' % (name, a, got)
+    assert len(L.SIGNATURES) >= 155 and list(L.LAB_SIGNATURES) == ['psnd_env_refresh']
+
+
 def test_mirrored_structs_match_the_header(L):
-    """the ctypes mirrors of the header's descriptor structs: same field names in the same order; psnd_wnorm_desc is 7 pointers + 6 ints"""
-    txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
-    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    bodies = dict(re.findall(r'typedef struct (psnd_\w+) \{(.*?)\} \1;', txt, flags=re.S))
+    """the ctypes classes of the header's descriptor structs: same field names in the same order; psnd_wnorm_desc is 7 pointers + 6 ints"""
+    bodies = dict(re.findall(r'typedef struct (psnd_\w+) \{(.*?)\} \1;', _header_text(), flags=re.S))
     for name, mirror in (('psnd_wgrad_desc', L.WgradDesc), ('psnd_chain_pair', L.ChainPair), ('psnd_wnorm_desc', L.WnormDesc)):
         declared = [re.search(r'(\w+)\s*$', f).group(1) for decl in bodies[name].split(';') for f in decl.split(',') if f.strip()]
         assert [f for f, _ in mirror._fields_] == declared, name
-    assert ctypes.sizeof(L.WnormDesc) == 80
+    assert ctypes.sizeof(L.WnormDesc) == 80                          # x86-64 LP64, the GPU hosts' ABI
+    assert ctypes.sizeof(L.WgradDesc) == 56
+    assert ctypes.sizeof(L.ChainPair) == 112
+    assert [t for _, t in L.WnormDesc._fields_] == [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6
+
+
+def test_constants_equal_the_header(L):
+    """every Python constant that stands for a header macro, against this file's own reading of the #define lines and the pinned literals"""
+    from pytorch_sound_amd import kernels as K
+    macros = {n: int(v) for n, v in re.findall(r'^#define (PSND_\w+) \(?(-?\d+)\)?\s*$', _header_text(), flags=re.M)}
+    assert macros == L.DEFINES
+    pinned = dict(PSND_OK=0, PSND_E_ARG=-1, PSND_E_SHAPE=-2, PSND_E_HIP=-3, PSND_E_UNSUPPORTED=-4,
+                  PSND_FRAMING_CENTER=0, PSND_FRAMING_HIFIGAN=1, PSND_FRAMING_NONE=2, PSND_LOG_NONE=0, PSND_LOG_E=1, PSND_LOG_10=2,
+                  PSND_MASK_NONE=0, PSND_MASK_LINEAR=1, PSND_MASK_SIGMOID=2, PSND_WNORM_MAX=32,
+                  PSND_IPREEMPH_SPAN=8192, PSND_IPREEMPH_WARM_MAX=2048, PSND_IPREEMPH_SEQ=-1, PSND_IPREEMPH_AUTO=-2,
+                  PSND_LFILTER_SPAN=8192, PSND_LFILTER_CHUNK=32, PSND_LFILTER_PARALLEL=0, PSND_LFILTER_SEQ=1,
+                  PSND_RESAMPLE_TILE=1024, PSND_RESAMPLE_MAX_TAPS=12801, PSND_SILENCE_BLOCK=1024)
+    assert macros == pinned
+    for mod, prefix, names in ((L, 'PSND_', ('PSND_OK', 'FRAMING_CENTER', 'FRAMING_HIFIGAN', 'FRAMING_NONE', 'LOG_NONE', 'LOG_E', 'LOG_10',
+                                             'MASK_NONE', 'MASK_LINEAR', 'MASK_SIGMOID')),
+                               (K, 'PSND_', ('IPREEMPH_SPAN', 'IPREEMPH_WARM_MAX', 'IPREEMPH_SEQ', 'IPREEMPH_AUTO', 'LFILTER_SPAN',
+                                             'LFILTER_PARALLEL', 'LFILTER_SEQ', 'RESAMPLE_TILE', 'RESAMPLE_MAX_TAPS', 'SILENCE_BLOCK'))):
+        for n in names:
+            assert getattr(mod, n) == macros[n if n.startswith(prefix) else prefix + n], n
+    assert 'PSND_GN_WS_DOUBLES' not in L.DEFINES and 'PSND_H' not in L.DEFINES
+
+
+# ---- the binding's parser refuses what it cannot type (header TEXT in, no library needed) --------------------------------------------------
+GOOD = 'int psnd_a(const float *x, int64_t n, void *stream);\n'
+
+
+@pytest.mark.parametrize('text,offender', [
+    (GOOD + 'int psnd_b(long double x, void *stream);\n', 'psnd_b'),                                   # a type word outside the grammar
+    (GOOD + 'long psnd_b(int x);\n', 'psnd_b'),                                                        # ... as the return type
+    (GOOD + 'typedef struct psnd_s {\n    const void *p, *q;\n    long double w;\n} psnd_s;\n', 'psnd_s'),     # a struct field
+    (GOOD + '#define PSND_X (1 << 3)\n', 'PSND_X'),                                                    # not an integer literal
+    (GOOD + '#define PSND_Y PSND_OK\n', 'PSND_Y'),
+    ('int psnd_b(int x)\n' + GOOD, 'psnd_b'),                                                          # two prototypes run together
+    (GOOD + 'int psnd_b(int x)\n', 'psnd_b'),                                                          # the last one left open
+    (GOOD + '#if 0\nint psnd_b(int x);\n#endif\n', '#if 0'),                                           # a block it would read as live
+])
+def test_parser_refuses_what_it_cannot_type(text, offender):
+    from pytorch_sound_amd import _lib
+    assert list(_lib.parse_header(GOOD)[0]) == ['psnd_a']
+    with pytest.raises(_lib.PsndError, match=re.escape(offender)):
+        _lib.parse_header(text)
+
+
+def test_parser_refuses_the_real_header_with_a_semicolon_removed():
+    from pytorch_sound_amd import _lib
+    txt = open(os.path.join(ROOT, 'include', 'psnd.h')).read()
+    sigs, lab, structs, defines = _lib.parse_header(txt)
+    assert len(sigs) == len(_lib.SIGNATURES) and sorted(structs) == ['psnd_chain_pair', 'psnd_wgrad_desc', 'psnd_wnorm_desc']
+    for name in ('psnd_lfilter', 'psnd_version', 'psnd_l1_loss_bwd_w', 'psnd_conv1d_cl_wgrad_multi_splits'):
+        m = re.search(r'\b%s\s*\([^()]*\)\s*;' % name, txt)
+        broken = txt[:m.end() - 1] + txt[m.end():]
+        with pytest.raises(_lib.PsndError, match=name):
+            _lib.parse_header(broken)
+
+
+def test_a_missing_header_is_an_error_that_names_the_path(monkeypatch):
+    from pytorch_sound_amd import _lib
+    monkeypatch.setattr(_lib, 'HEADER_PATH', '/nonexistent/include/psnd.h')
+    with pytest.raises(_lib.PsndError, match='/nonexistent/include/psnd.h'):
+        _lib._read_header()
 
 
 def test_frame_contract_matches_oracle(L):

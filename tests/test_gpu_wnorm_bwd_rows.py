@@ -37,13 +37,6 @@ CASES = {
 }
 
 
-class WnormDesc(ctypes.Structure):
-    """psnd_wnorm_desc of include/psnd.h"""
-    _fields_ = [('gw_part', ctypes.c_void_p), ('gbias_part', ctypes.c_void_p), ('v', ctypes.c_void_p), ('g', ctypes.c_void_p),
-                ('gv', ctypes.c_void_p), ('gg', ctypes.c_void_p), ('gbias', ctypes.c_void_p),
-                ('splits', ctypes.c_int), ('Cout', ctypes.c_int), ('Cin', ctypes.c_int), ('k', ctypes.c_int), ('Cb', ctypes.c_int), ('Ca', ctypes.c_int)]
-
-
 def case_inputs(name):
     """per conv (gw_part (S, k, Cb, Ca), gbias_part (S, Cb), v (Cout, Cin, k), g (Cout)) from a fixed seed; a few slab values are -0, 0
     and large, so that the zero terms of the sums and their order show in the bits"""
@@ -68,7 +61,7 @@ def guarded(numel, guard):
 
 def run_case(name, entry=None):
     """launch the case; returns per conv (gv, gg, gbias or None) as numpy arrays and asserts that every guard region is intact"""
-    from pytorch_sound_amd._lib import lib, ptr, stream_ptr, check
+    from pytorch_sound_amd._lib import lib, ptr, stream_ptr, check, WnormDesc
     entry = entry or CASES[name][0]
     convs = CASES[name][1]
     keep, outs, descs = [], [], (WnormDesc * len(convs))()

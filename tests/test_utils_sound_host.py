@@ -179,12 +179,8 @@ def test_abi_symbols_are_exported_declared_and_mirrored(L):
         names = [re.search(r'(\w+)$', s).group(1) for s in args]
         assert names[-len(last):] == last
         assert hasattr(h, name)
-        res, argtypes = L.SIGNATURES[name]
+        res, argtypes = L.SIGNATURES[name]        # every argument type: tests/test_cabi.py, test_every_signature_matches_the_header
         assert res is (ctypes.c_int if ret == 'int' else ctypes.c_int64) and len(argtypes) == len(args)
-        for s, t in zip(args, argtypes):
-            kind = (ctypes.c_void_p if '*' in s else ctypes.c_double if s.startswith('double') else ctypes.c_float if s.startswith('float')
-                    else ctypes.c_int64 if s.startswith('int64_t') else ctypes.c_int)
-            assert t is kind, (s, t)
     for macro, value in (('PSND_LFILTER_SPAN', 8192), ('PSND_LFILTER_CHUNK', 32), ('PSND_LFILTER_PARALLEL', 0), ('PSND_LFILTER_SEQ', 1)):
         assert re.search(r'#define %s %d\b' % (macro, value), txt), macro
     from pytorch_sound_amd import kernels as K
