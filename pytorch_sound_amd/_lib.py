@@ -6,6 +6,7 @@ import ctypes
 import os
 import re
 import numpy as np
+import torch        # before libpsnd_hip.so is loaded (lib), and the base of the launcher's device guard (on)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PSND_LIB', os.path.join(_HERE, 'libpsnd_hip.so'))   # PSND_LIB: A/B builds of the same ABI
@@ -32,8 +33,9 @@ def _scalar(words, decl):
     return _SCALARS[words[0]]
 
 
-def _prototypes(text):
-    """`ret psnd_name(args);` declarations and nothing else -> {name: (restype, [argtypes])}"""
+def _prototypes(text, streamed):
+    """`ret psnd_name(args);` declarations and nothing else -> {name: (restype, [argtypes])}; the names of those that return an int status
+    and whose last parameter is `void *stream` are added to the set `streamed`"""
     *decls, tail = text.split(';')
     if tail.strip():
         raise PsndError('include/psnd.h: `%s` is not closed by a `;`' % ' '.join(tail.split()))
@@ -45,6 +47,8 @@ def _prototypes(text):
             raise PsndError('include/psnd.h: cannot read `%s` as one prototype of a known return type' % decl)
         args = [] if m.group(3).strip() == 'void' else [a.strip() for a in m.group(3).split(',')]
         out[m.group(2)] = (_RETURNS[ret], [_P if '*' in a else _scalar(a.split()[:-1], decl) for a in args])
+        if ret == 'int' and args and re.fullmatch(r'void ?\* ?stream', args[-1]):
+            streamed.add(m.group(2))
     return out
 
 
@@ -62,9 +66,10 @@ def _fields(name, body):
     return out
 
 
-def parse_header(text):
+def parse_header(text, streamed=None):
     """the text of include/psnd.h -> (signatures, lab signatures, {struct: [(field, ctype)]}, {macro: int}); raises PsndError on anything
-    outside the grammar instead of skipping it"""
+    outside the grammar instead of skipping it.  streamed: a set that receives the names of the entry points that launch on a stream"""
+    streamed = set() if streamed is None else streamed
     text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
     defines = {}
     for name, params, body in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(\w+)(\(?)([^\n]*)', text, flags=re.M):
@@ -82,19 +87,20 @@ def parse_header(text):
     text = re.sub(r'^[ \t]*#[^\n]*', ' ', text, flags=re.M)
     struct = r'typedef struct (psnd_\w+) \{(.*?)\} \1;'
     structs = {name: _fields(name, body) for name, body in re.findall(struct, text, flags=re.S)}
-    return _prototypes(re.sub(struct, ' ', text, flags=re.S)), _prototypes(lab), structs, defines
+    return _prototypes(re.sub(struct, ' ', text, flags=re.S), streamed), _prototypes(lab, streamed), structs, defines
 
 
-def _read_header():
+def _read_header(streamed=None):
     try:
         with open(HEADER_PATH) as f:
-            return parse_header(f.read())
+            return parse_header(f.read(), streamed)
     except OSError as e:
         raise PsndError('include/psnd.h not found at %s (%s): the binding is derived from it' % (HEADER_PATH, e))
 
 
 # name -> (restype, argtypes) of every entry point / of those of a -DPSND_LAB build only; struct -> fields; PSND_* macro -> value
-SIGNATURES, LAB_SIGNATURES, _STRUCTS, DEFINES = _read_header()
+LAUNCHABLE = set()          # the entry points `on` serves: int psnd_name(..., void *stream)
+SIGNATURES, LAB_SIGNATURES, _STRUCTS, DEFINES = _read_header(LAUNCHABLE)
 
 
 def _struct(name):
@@ -118,8 +124,7 @@ def lib():
     if _lib is None:
         # torch bundles its own libamdhip64: it must be in the process BEFORE our library is
         # dlopen'ed, otherwise the dynamic linker binds us to a second HIP runtime (/opt/rocm) that
-        # never sees torch's device context ("no ROCm-capable device is detected").
-        import torch  # noqa: F401
+        # never sees torch's device context ("no ROCm-capable device is detected").  This module imports torch at its top.
         if not os.path.exists(LIB_PATH):
             raise PsndError('libpsnd_hip.so not found at %s - run `python -m pytorch_sound_amd._build` '
                             '(there is no CPU / eager fallback)' % LIB_PATH)
@@ -194,8 +199,57 @@ def np_ptr(a):
 
 
 def stream_ptr(device):
-    import torch
     return _P(torch.cuda.current_stream(device).cuda_stream)
+
+
+class on(torch.cuda.device):
+    """the one launch path from Python to the library:
+
+        with on(x.device) as hip:
+            hip.psnd_posenc(x, pe, scale, N, C, T, Tp, y)
+
+    Entering makes `device` current as torch.cuda.device does and takes that device's current stream ONCE - the side stream under
+    torch.cuda.stream(side), the capture stream during a hipGraph capture - so a block never spans a change of the current stream: open a
+    nested `on` inside the torch.cuda.stream block instead.  hip.psnd_name(*args) calls that entry point of the library loaded at that
+    moment (use_library is followed) with the stream appended, and raises PsndError on a non-zero status.  Where include/psnd.h types a
+    parameter as a pointer a tensor becomes its data_ptr(); None (NULL), ctypes objects and int addresses pass as they are.  Only the entry
+    points of LAUNCHABLE are served: the others (psnd_*_bytes, plan builders ...) take no stream and are called as lib().psnd_name(...)."""
+
+    def __enter__(self):
+        super().__enter__()
+        self.stream = torch.cuda.current_stream().cuda_stream
+        return self
+
+    def __getattr__(self, name):            # reached only by names that are no launch method (_launch_method, below)
+        if name in SIGNATURES or name in LAB_SIGNATURES:
+            raise PsndError('%s takes no stream: call it as lib().%s(...)' % (name, name))
+        raise AttributeError('%s is not an entry point of include/psnd.h that `on` serves' % name)
+
+
+def _launch_method(name):
+    """on.psnd_name: a plain method, so that a launch costs one attribute lookup and one Python call.  The pointer positions are worked out
+    here, once; the handle keeps the functions it has looked up (ctypes); ctypes gets plain ints."""
+    argtypes = (SIGNATURES.get(name) or LAB_SIGNATURES[name])[1]
+    n = len(argtypes) - 1
+    pointers = [i for i in range(n) if argtypes[i] is _P]
+
+    def launch(self, *args):
+        fn = getattr(lib(), name)       # of the handle loaded now (use_library swaps it); AttributeError: a lab entry point, a product build
+        if len(args) != n:
+            raise TypeError('%s takes %d arguments and the stream, got %d' % (name, n, len(args)))
+        args = list(args)
+        for i in pointers:
+            if isinstance(args[i], torch.Tensor):
+                args[i] = args[i].data_ptr()
+        rc = fn(*args, self.stream)
+        if rc != PSND_OK:
+            check(rc, name)
+    launch.__name__ = launch.__qualname__ = name
+    return launch
+
+
+for _name in LAUNCHABLE:
+    setattr(on, _name, _launch_method(_name))
 
 
 def frame_count(T, n_fft, hop, framing=FRAMING_CENTER):

@@ -19,7 +19,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import lib, check, ptr, stream_ptr
+from ._lib import lib, ptr, on
 
 ALIGN_C = 32
 
@@ -56,9 +56,8 @@ class ToCL(torch.autograd.Function):
         N, C, T = x.shape
         Cp = round_up(C, ALIGN_C)
         out = torch.empty((N, shape.Lp, Cp), dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_to_cl(ptr(x), N, C, T, shape.Lp, shape.HP, Cp, int(preop), ptr(out), stream_ptr(x.device)),
-                  'psnd_to_cl')
+        with on(x.device) as hip:
+            hip.psnd_to_cl(x, N, C, T, shape.Lp, shape.HP, Cp, int(preop), out)
         ctx.shape, ctx.C, ctx.T, ctx.preop = shape, C, T, preop
         if preop:
             ctx.save_for_backward(x)
@@ -78,8 +77,8 @@ def from_cl_raw(buf, C, T, shape):
     _need(buf, torch.bfloat16)
     N, Lp, Cp = buf.shape
     out = torch.empty((N, C, T), dtype=torch.float32, device=buf.device)
-    with torch.cuda.device(buf.device):
-        check(lib().psnd_from_cl(ptr(buf), N, C, T, Lp, shape.HP, Cp, ptr(out), stream_ptr(buf.device)), 'psnd_from_cl')
+    with on(buf.device) as hip:
+        hip.psnd_from_cl(buf, N, C, T, Lp, shape.HP, Cp, out)
     return out
 
 
@@ -94,9 +93,8 @@ class FromCL(torch.autograd.Function):
         g = g.contiguous()
         N, C, T = g.shape
         out = torch.empty((N, ctx.shape.Lp, ctx.Cp), dtype=torch.bfloat16, device=g.device)
-        with torch.cuda.device(g.device):
-            check(lib().psnd_to_cl(ptr(g), N, C, T, ctx.shape.Lp, ctx.shape.HP, ctx.Cp, 0, ptr(out), stream_ptr(g.device)),
-                  'psnd_to_cl')
+        with on(g.device) as hip:
+            hip.psnd_to_cl(g, N, C, T, ctx.shape.Lp, ctx.shape.HP, ctx.Cp, 0, out)
         return out, None, None, None
 
 
@@ -110,8 +108,8 @@ class FromCLTanh(torch.autograd.Function):
         _need(buf, torch.bfloat16)
         N, Lp, Cp = buf.shape
         out = torch.empty((N, C, T), dtype=torch.float32, device=buf.device)
-        with torch.cuda.device(buf.device):
-            check(lib().psnd_from_cl_tanh(ptr(buf), N, C, T, Lp, shape.HP, Cp, ptr(out), stream_ptr(buf.device)), 'psnd_from_cl_tanh')
+        with on(buf.device) as hip:
+            hip.psnd_from_cl_tanh(buf, N, C, T, Lp, shape.HP, Cp, out)
         ctx.shape, ctx.Cp = shape, Cp
         ctx.save_for_backward(out)
         return out
@@ -122,9 +120,8 @@ class FromCLTanh(torch.autograd.Function):
         g = g.contiguous().float()
         N, C, T = g.shape
         gx = torch.empty((N, ctx.shape.Lp, ctx.Cp), dtype=torch.bfloat16, device=g.device)
-        with torch.cuda.device(g.device):
-            check(lib().psnd_to_cl_tanh_bwd(ptr(g), ptr(out), N, C, T, ctx.shape.Lp, ctx.shape.HP, ctx.Cp, ptr(gx), stream_ptr(g.device)),
-                  'psnd_to_cl_tanh_bwd')
+        with on(g.device) as hip:
+            hip.psnd_to_cl_tanh_bwd(g, out, N, C, T, ctx.shape.Lp, ctx.shape.HP, ctx.Cp, gx)
         return gx, None, None, None
 
 
@@ -139,9 +136,8 @@ class MaskHeadCL(torch.autograd.Function):
         y, mag = y.contiguous(), mag.contiguous()
         N, C, T = mag.shape
         est = torch.empty_like(mag)
-        with torch.cuda.device(y.device):
-            check(lib().psnd_mask_head_fwd(ptr(y), ptr(mag), N, C, T, shape.Lp, shape.HP, y.shape[2], ptr(est), stream_ptr(y.device)),
-                  'psnd_mask_head_fwd')
+        with on(y.device) as hip:
+            hip.psnd_mask_head_fwd(y, mag, N, C, T, shape.Lp, shape.HP, y.shape[2], est)
         ctx.shape = shape
         ctx.save_for_backward(y, mag)
         return est
@@ -152,9 +148,8 @@ class MaskHeadCL(torch.autograd.Function):
         g = g.contiguous().float()
         N, C, T = mag.shape
         gy = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            check(lib().psnd_mask_head_bwd(ptr(g), ptr(mag), ptr(y), N, C, T, ctx.shape.Lp, ctx.shape.HP, y.shape[2], ptr(gy),
-                                           stream_ptr(y.device)), 'psnd_mask_head_bwd')
+        with on(y.device) as hip:
+            hip.psnd_mask_head_bwd(g, mag, y, N, C, T, ctx.shape.Lp, ctx.shape.HP, y.shape[2], gy)
         return gy, None, None
 
 
@@ -173,6 +168,58 @@ def _nan_flag_tensor(dev):
     return torch.empty((), dtype=torch.float32, device=dev)
 
 
+def _spectral_l1_forward(nfk, ctx, y, mag, mag_ref, mel_ref, mel_plan, shape, M, log_kind, log_offset, pre_clamp_min, clamp_lo, clamp_hi, w1, w2):
+    """forward of MaskHeadSpectralL1CL (nfk False: mag / mag_ref / est are (N, K, F)) and MaskHeadSpectralL1NFK (True: (N, F, K), the
+    psnd_*_nfk twins of the same entry points)"""
+    from .kernels import _clamp_args
+    ctx.set_materialize_grads(False)             # `est` (no gradient of its own) must not cost a zero fill of its size in backward
+    _need(y, torch.bfloat16)
+    for t in (mag, mag_ref, mel_ref):
+        _need(t, torch.float32)
+    N, F, K = mag.shape if nfk else (mag.shape[0], mag.shape[2], mag.shape[1])
+    if mag_ref.shape != mag.shape or tuple(mel_ref.shape) != (N, M, F):
+        raise _lib.PsndError('mask_head_spectral_l1%s: mag_ref %s / mel_ref %s do not match mag %s and %d mel bands'
+                             % (' (nfk)' if nfk else '', tuple(mag_ref.shape), tuple(mel_ref.shape), tuple(mag.shape), M))
+    dev = y.device
+    lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
+    est = torch.empty_like(mag)
+    lin = torch.empty((N, M, F), dtype=torch.float32, device=dev)
+    nb1 = int(lib().psnd_mask_head_l1_blocks_nfk(N, F, K) if nfk else lib().psnd_mask_head_l1_blocks(N, F, y.shape[2]))
+    nb2 = int(lib().psnd_mel_l1_blocks(N, F, M))
+    part = torch.empty(nb1 + nb2, dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    with on(dev) as hip:
+        head, mel = (hip.psnd_mask_head_l1_fwd_nfk, hip.psnd_mel_l1_fwd_nfk) if nfk else (hip.psnd_mask_head_l1_fwd, hip.psnd_mel_l1_fwd)
+        head(y, mag, mag_ref, N, K, F, shape.Lp, shape.HP, y.shape[2], est, part)
+        mel(est, N, F, M, K, mel_plan, log_kind, float(log_offset), pre, lo, hi, mel_ref, lin, part.data_ptr() + 8 * nb1)
+        parts = (ctypes.c_void_p * 2)(part.data_ptr(), part.data_ptr() + 8 * nb1)
+        nbs = (ctypes.c_int64 * 2)(nb1, nb2)
+        sc = (ctypes.c_double * 2)(float(w1) / mag.numel(), float(w2) / mel_ref.numel())
+        nan_flag = _nan_flag_tensor(dev)
+        hip.psnd_l1_loss_combine(parts, nbs, sc, 2, out, nan_flag)
+    LAST_LOSS_NAN_FLAG[0] = nan_flag
+    ctx.cfg = (shape, M, log_kind, float(log_offset), pre, lo, hi, float(w1) / mag.numel(), float(w2) / mel_ref.numel())
+    ctx.save_for_backward(y, mag, mag_ref, mel_ref, mel_plan, est, lin)
+    ctx.mark_non_differentiable(est)
+    return out, est
+
+
+def _spectral_l1_backward(nfk, ctx, g):
+    y, mag, mag_ref, mel_ref, mel_plan, est, lin = ctx.saved_tensors
+    shape, M, log_kind, log_offset, pre, lo, hi, c1, c2 = ctx.cfg
+    N, F, K = mag.shape if nfk else (mag.shape[0], mag.shape[2], mag.shape[1])
+    if g is None:
+        return (None,) * 14
+    g = g.contiguous().float()
+    gest = torch.empty_like(mag)
+    gy = torch.empty_like(y)
+    with on(y.device) as hip:
+        mel, head = (hip.psnd_mel_l1_bwd_nfk, hip.psnd_mask_head_l1_bwd_nfk) if nfk else (hip.psnd_mel_l1_bwd, hip.psnd_mask_head_l1_bwd)
+        mel(mel_ref, lin, g, c2, N, F, M, K, mel_plan, log_kind, log_offset, pre, lo, hi, gest)
+        head(gest, mag, y, est, mag_ref, g, c1, N, K, F, shape.Lp, shape.HP, y.shape[2], gy)
+    return (gy,) + (None,) * 13
+
+
 class MaskHeadSpectralL1CL(torch.autograd.Function):
     """w1 * F.l1_loss(est, mag_ref) + w2 * F.l1_loss(log_mel(est), mel_ref) with est = sigmoid(from_cl(y)) * mag - a masking recipe's
     loss as ONE autograd node over four launches forward (mask head with the first term's partial sums, mel projection with the second
@@ -183,59 +230,12 @@ class MaskHeadSpectralL1CL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, mag, mag_ref, mel_ref, mel_plan, shape, M, log_kind, log_offset, pre_clamp_min, clamp_lo, clamp_hi, w1, w2):
-        import ctypes
-        from .kernels import _clamp_args
-        ctx.set_materialize_grads(False)             # `est` (no gradient of its own) must not cost a zero fill of its size in backward
-        _need(y, torch.bfloat16)
-        for t in (mag, mag_ref, mel_ref):
-            _need(t, torch.float32)
-        N, C, T = mag.shape
-        if mag_ref.shape != mag.shape or tuple(mel_ref.shape) != (N, M, T):
-            raise _lib.PsndError('mask_head_spectral_l1: mag_ref %s / mel_ref %s do not match mag %s and %d mel bands'
-                                 % (tuple(mag_ref.shape), tuple(mel_ref.shape), tuple(mag.shape), M))
-        dev = y.device
-        lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
-        est = torch.empty_like(mag)
-        lin = torch.empty((N, M, T), dtype=torch.float32, device=dev)
-        nb1 = int(lib().psnd_mask_head_l1_blocks(N, T, y.shape[2]))
-        nb2 = int(lib().psnd_mel_l1_blocks(N, T, M))
-        part = torch.empty(nb1 + nb2, dtype=torch.float64, device=dev)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        st = stream_ptr(dev)
-        with torch.cuda.device(dev):
-            check(lib().psnd_mask_head_l1_fwd(ptr(y), ptr(mag), ptr(mag_ref), N, C, T, shape.Lp, shape.HP, y.shape[2], ptr(est),
-                                              ptr(part), st), 'psnd_mask_head_l1_fwd')
-            p2 = ctypes.c_void_p(part.data_ptr() + 8 * nb1)
-            check(lib().psnd_mel_l1_fwd(ptr(est), N, T, M, C, ptr(mel_plan), log_kind, float(log_offset), pre, lo, hi, ptr(mel_ref),
-                                        ptr(lin), p2, st), 'psnd_mel_l1_fwd')
-            parts = (ctypes.c_void_p * 2)(part.data_ptr(), part.data_ptr() + 8 * nb1)
-            nbs = (ctypes.c_int64 * 2)(nb1, nb2)
-            sc = (ctypes.c_double * 2)(float(w1) / mag.numel(), float(w2) / mel_ref.numel())
-            nan_flag = _nan_flag_tensor(dev)
-            check(lib().psnd_l1_loss_combine(parts, nbs, sc, 2, ptr(out), ptr(nan_flag), st), 'psnd_l1_loss_combine')
-        LAST_LOSS_NAN_FLAG[0] = nan_flag
-        ctx.cfg = (shape, M, log_kind, float(log_offset), pre, lo, hi, float(w1) / mag.numel(), float(w2) / mel_ref.numel())
-        ctx.save_for_backward(y, mag, mag_ref, mel_ref, mel_plan, est, lin)
-        ctx.mark_non_differentiable(est)
-        return out, est
+        return _spectral_l1_forward(False, ctx, y, mag, mag_ref, mel_ref, mel_plan, shape, M, log_kind, log_offset, pre_clamp_min, clamp_lo,
+                                    clamp_hi, w1, w2)
 
     @staticmethod
     def backward(ctx, g, _gest):
-        y, mag, mag_ref, mel_ref, mel_plan, est, lin = ctx.saved_tensors
-        shape, M, log_kind, log_offset, pre, lo, hi, c1, c2 = ctx.cfg
-        N, C, T = mag.shape
-        if g is None:
-            return (None,) * 14
-        g = g.contiguous().float()
-        gest = torch.empty_like(mag)
-        gy = torch.empty_like(y)
-        st = stream_ptr(y.device)
-        with torch.cuda.device(y.device):
-            check(lib().psnd_mel_l1_bwd(ptr(mel_ref), ptr(lin), ptr(g), c2, N, T, M, C, ptr(mel_plan), log_kind, log_offset, pre, lo, hi,
-                                        ptr(gest), st), 'psnd_mel_l1_bwd')
-            check(lib().psnd_mask_head_l1_bwd(ptr(gest), ptr(mag), ptr(y), ptr(est), ptr(mag_ref), ptr(g), c1, N, C, T, shape.Lp, shape.HP,
-                                              y.shape[2], ptr(gy), st), 'psnd_mask_head_l1_bwd')
-        return (gy,) + (None,) * 13
+        return _spectral_l1_backward(False, ctx, g)
 
 
 def to_cl_nfk(x_nfk, shape, preop=0):
@@ -249,9 +249,8 @@ def to_cl_nfk(x_nfk, shape, preop=0):
         raise _lib.PsndError('to_cl_nfk: tensor %s does not match the CL geometry (N=%d, L=%d)' % (tuple(x_nfk.shape), shape.N, shape.L))
     Cp = round_up(K, ALIGN_C)
     out = torch.empty((N, shape.Lp, Cp), dtype=torch.bfloat16, device=x_nfk.device)
-    with torch.cuda.device(x_nfk.device):
-        check(lib().psnd_to_cl_nfk(ptr(x_nfk), N, K, F, shape.Lp, shape.HP, Cp, int(preop), ptr(out), stream_ptr(x_nfk.device)),
-              'psnd_to_cl_nfk')
+    with on(x_nfk.device) as hip:
+        hip.psnd_to_cl_nfk(x_nfk, N, K, F, shape.Lp, shape.HP, Cp, int(preop), out)
     return out
 
 
@@ -262,58 +261,12 @@ class MaskHeadSpectralL1NFK(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, mag, mag_ref, mel_ref, mel_plan, shape, M, log_kind, log_offset, pre_clamp_min, clamp_lo, clamp_hi, w1, w2):
-        from .kernels import _clamp_args
-        ctx.set_materialize_grads(False)
-        _need(y, torch.bfloat16)
-        for t in (mag, mag_ref, mel_ref):
-            _need(t, torch.float32)
-        N, F, K = mag.shape
-        if mag_ref.shape != mag.shape or tuple(mel_ref.shape) != (N, M, F):
-            raise _lib.PsndError('mask_head_spectral_l1 (nfk): mag_ref %s / mel_ref %s do not match mag %s and %d mel bands'
-                                 % (tuple(mag_ref.shape), tuple(mel_ref.shape), tuple(mag.shape), M))
-        dev = y.device
-        lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
-        est = torch.empty_like(mag)
-        lin = torch.empty((N, M, F), dtype=torch.float32, device=dev)
-        nb1 = int(lib().psnd_mask_head_l1_blocks_nfk(N, F, K))
-        nb2 = int(lib().psnd_mel_l1_blocks(N, F, M))
-        part = torch.empty(nb1 + nb2, dtype=torch.float64, device=dev)
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        st = stream_ptr(dev)
-        with torch.cuda.device(dev):
-            check(lib().psnd_mask_head_l1_fwd_nfk(ptr(y), ptr(mag), ptr(mag_ref), N, K, F, shape.Lp, shape.HP, y.shape[2], ptr(est),
-                                                  ptr(part), st), 'psnd_mask_head_l1_fwd_nfk')
-            p2 = ctypes.c_void_p(part.data_ptr() + 8 * nb1)
-            check(lib().psnd_mel_l1_fwd_nfk(ptr(est), N, F, M, K, ptr(mel_plan), log_kind, float(log_offset), pre, lo, hi, ptr(mel_ref),
-                                            ptr(lin), p2, st), 'psnd_mel_l1_fwd_nfk')
-            parts = (ctypes.c_void_p * 2)(part.data_ptr(), part.data_ptr() + 8 * nb1)
-            nbs = (ctypes.c_int64 * 2)(nb1, nb2)
-            sc = (ctypes.c_double * 2)(float(w1) / mag.numel(), float(w2) / mel_ref.numel())
-            nan_flag = _nan_flag_tensor(dev)
-            check(lib().psnd_l1_loss_combine(parts, nbs, sc, 2, ptr(out), ptr(nan_flag), st), 'psnd_l1_loss_combine')
-        LAST_LOSS_NAN_FLAG[0] = nan_flag
-        ctx.cfg = (shape, M, log_kind, float(log_offset), pre, lo, hi, float(w1) / mag.numel(), float(w2) / mel_ref.numel())
-        ctx.save_for_backward(y, mag, mag_ref, mel_ref, mel_plan, est, lin)
-        ctx.mark_non_differentiable(est)
-        return out, est
+        return _spectral_l1_forward(True, ctx, y, mag, mag_ref, mel_ref, mel_plan, shape, M, log_kind, log_offset, pre_clamp_min, clamp_lo,
+                                    clamp_hi, w1, w2)
 
     @staticmethod
     def backward(ctx, g, _gest):
-        y, mag, mag_ref, mel_ref, mel_plan, est, lin = ctx.saved_tensors
-        shape, M, log_kind, log_offset, pre, lo, hi, c1, c2 = ctx.cfg
-        N, F, K = mag.shape
-        if g is None:
-            return (None,) * 14
-        g = g.contiguous().float()
-        gest = torch.empty_like(mag)
-        gy = torch.empty_like(y)
-        st = stream_ptr(y.device)
-        with torch.cuda.device(y.device):
-            check(lib().psnd_mel_l1_bwd_nfk(ptr(mel_ref), ptr(lin), ptr(g), c2, N, F, M, K, ptr(mel_plan), log_kind, log_offset, pre, lo, hi,
-                                            ptr(gest), st), 'psnd_mel_l1_bwd_nfk')
-            check(lib().psnd_mask_head_l1_bwd_nfk(ptr(gest), ptr(mag), ptr(y), ptr(est), ptr(mag_ref), ptr(g), c1, N, K, F, shape.Lp,
-                                                  shape.HP, y.shape[2], ptr(gy), st), 'psnd_mask_head_l1_bwd_nfk')
-        return (gy,) + (None,) * 13
+        return _spectral_l1_backward(True, ctx, g)
 
 
 def _launch_conv(A, A2, AM, a2_slope, W, bias, res, mask_src, shape, Ca, Cb, k, off0, dstep, act_slope, mask_slope,
@@ -321,10 +274,9 @@ def _launch_conv(A, A2, AM, a2_slope, W, bias, res, mask_src, shape, Ca, Cb, k, 
     dev = W.device
     raw = torch.empty((shape.N, shape.Lp, Cb), dtype=torch.bfloat16, device=dev) if want_raw else None
     act = torch.empty((shape.N, shape.Lp, Cb), dtype=torch.bfloat16, device=dev) if want_act else None
-    with torch.cuda.device(dev):
-        check(lib().psnd_conv1d_cl(ptr(A), ptr(A2), ptr(AM), float(a2_slope), ptr(W), ptr(bias), ptr(res), ptr(mask_src),
-                                   shape.N, shape.Lp, shape.L, shape.HP, Ca, Cb, k, off0, dstep, float(act_slope),
-                                   float(mask_slope), ptr(raw), ptr(act), ptr(a_eff_out), stream_ptr(dev)), 'psnd_conv1d_cl')
+    with on(dev) as hip:
+        hip.psnd_conv1d_cl(A, A2, AM, float(a2_slope), W, bias, res, mask_src, shape.N, shape.Lp, shape.L, shape.HP, Ca, Cb, k, off0, dstep,
+                           float(act_slope), float(mask_slope), raw, act, a_eff_out)
     return raw, act
 
 
@@ -646,9 +598,8 @@ class FusedConvCL(torch.autograd.Function):
             wb = torch.empty((k, Ca, Cb), dtype=torch.bfloat16, device=dev)      # [j][ci][co]
             bp = torch.empty(Cb, dtype=torch.float32, device=dev)
             b32 = None if bias is None else bias.detach().contiguous()
-            with torch.cuda.device(dev):
-                check(lib().psnd_conv1d_prep(ptr(v32), ptr(g32), ptr(b32), Cout, Cin, k, Cb, Ca, ptr(wf), ptr(wb), ptr(bp),
-                                             stream_ptr(dev)), 'psnd_conv1d_prep')
+            with on(dev) as hip:
+                hip.psnd_conv1d_prep(v32, g32, b32, Cout, Cin, k, Cb, Ca, wf, wb, bp)
         raw, act = _launch_conv(xa, None, None, 1.0, wf, bp, res, None, shape, Ca, Cb, k, -pad, dil, act_slope, 1.0,
                                 want_raw, want_act)
         ctx.shape, ctx.dil, ctx.k, ctx.pad, ctx.act_slope = shape, dil, k, pad, act_slope
@@ -677,12 +628,10 @@ class FusedConvCL(torch.autograd.Function):
         gv = torch.empty_like(v32)
         gg = torch.empty_like(g32)
         gx = torch.empty((shape.N, shape.Lp, Ca), dtype=torch.bfloat16, device=dev)
-        with torch.cuda.device(dev):
-            check(lib().psnd_conv1d_cl_bwd(ptr(g_raw), ptr(g_act), ptr(am), float(ctx.act_slope), ptr(wb), ptr(xa), shape.N,
-                                           shape.Lp, shape.L, shape.HP, Ca, Cb, k, pad, dil, ptr(gx), ptr(g_out), None, 1.0, None,
-                                           ptr(gw), ptr(gbp), stream_ptr(dev)), 'psnd_conv1d_cl_bwd')
-            check(lib().psnd_conv1d_wnorm_bwd(ptr(gw), ptr(gbp), S, ptr(v32), ptr(g32), Cout, Cin, k, Cb, Ca, ptr(gv),
-                                              ptr(gg), ptr(gb), stream_ptr(dev)), 'psnd_conv1d_wnorm_bwd')
+        with on(dev) as hip:
+            hip.psnd_conv1d_cl_bwd(g_raw, g_act, am, float(ctx.act_slope), wb, xa, shape.N, shape.Lp, shape.L, shape.HP, Ca, Cb, k, pad, dil, gx,
+                                   g_out, None, 1.0, None, gw, gbp)
+            hip.psnd_conv1d_wnorm_bwd(gw, gbp, S, v32, g32, Cout, Cin, k, Cb, Ca, gv, gg, gb)
         g_res = None
         if ctx.has_res:
             g_res = g_out if need_gout else g_raw
@@ -749,13 +698,11 @@ class ConvTransposeCL(torch.autograd.Function):
         alloc = torch.empty if _up_covers(shape, out_shape, stride, padding) else torch.zeros
         both = alloc((2, shape.N, out_shape.Lp, Cr), dtype=torch.bfloat16, device=dev)
         raw, act = both[0], both[1]
-        with torch.cuda.device(dev):
-            st = stream_ptr(dev)
+        with on(dev) as hip:
             if prepped is None:
-                check(lib().psnd_convtr1d_prep(ptr(v32), ptr(g32), ptr(b32), Cin, Cout, K, stride, Cr, Cip, ptr(wf), ptr(wb), ptr(bp), st),
-                      'psnd_convtr1d_prep')
-            check(lib().psnd_convtr1d_cl_fwd(ptr(xa), ptr(wf), ptr(bp), shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr, stride, padding,
-                                             out_shape.Lp, out_shape.HP, float(act_slope), ptr(raw), ptr(act), st), 'psnd_convtr1d_cl_fwd')
+                hip.psnd_convtr1d_prep(v32, g32, b32, Cin, Cout, K, stride, Cr, Cip, wf, wb, bp)
+            hip.psnd_convtr1d_cl_fwd(xa, wf, bp, shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr, stride, padding, out_shape.Lp, out_shape.HP,
+                                     float(act_slope), raw, act)
         ctx.geo = (shape, out_shape, stride, padding, float(act_slope), Cin, Cout, K, Cip, Cr)
         ctx.has_bias = bias is not None
         ctx.params = (weight_v, weight_g, bias)
@@ -794,12 +741,10 @@ class ConvTransposeCL(torch.autograd.Function):
                 GRAD_SINK.note_producer(ctx.params, side)
         main = torch.cuda.current_stream(dev)
 
-        def param_side(st):
-            check(lib().psnd_convtr1d_cl_bwd(ptr(g_raw), ptr(g_act), ptr(act if g_act is not None else None), slope, ptr(wb), ptr(xa),
-                                             shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr, stride, padding, out_shape.Lp, out_shape.HP,
-                                             None, ptr(g_eff), ptr(gw), st), 'psnd_convtr1d_cl_bwd')
-            check(lib().psnd_convtr1d_wnorm_bwd(ptr(gw), S, ptr(v32), ptr(g32), Cin, Cout, K, stride, Cr, Cip, ptr(gv), ptr(gg), st),
-                  'psnd_convtr1d_wnorm_bwd')
+        def param_side(hip):
+            hip.psnd_convtr1d_cl_bwd(g_raw, g_act, act if g_act is not None else None, slope, wb, xa, shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr,
+                                     stride, padding, out_shape.Lp, out_shape.HP, None, g_eff, gw)
+            hip.psnd_convtr1d_wnorm_bwd(gw, S, v32, g32, Cin, Cout, K, stride, Cr, Cip, gv, gg)
             if ctx.has_bias:   # column sums of the combined gradient (halo rows are zero): psnd_cl_colsum, fp32, fixed order
                 gsrc = (g_eff if g_eff is not None else g_raw).view(-1, Cr)
                 if Cr > 256:   # (wider than the kernel's column groups: not a HiFi-GAN upsampler)
@@ -808,22 +753,21 @@ class ConvTransposeCL(torch.autograd.Function):
                 part = torch.empty(lib().psnd_cl_colsum_splits(rows, Cr) * Cr, dtype=torch.float32, device=dev)
                 gb_full = torch.empty(Cr, dtype=torch.float32, device=dev)
                 win = (out_shape.Lp, out_shape.HP, out_shape.HP + out_shape.L) if (g_eff is not None and clip_rows) else (0, 0, 0)
-                check(lib().psnd_cl_colsum(ptr(gsrc), rows, Cr, win[0], win[1], win[2], ptr(part), ptr(gb_full), st), 'psnd_cl_colsum')
+                hip.psnd_cl_colsum(gsrc, rows, Cr, win[0], win[1], win[2], part, gb_full)
                 return gb_full[:Cout]
             return None
 
-        with torch.cuda.device(dev):
-            check(lib().psnd_convtr1d_cl_bwd(ptr(g_raw), ptr(g_act), ptr(act if g_act is not None else None), slope, ptr(wb), ptr(xa),
-                                             shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr, stride, padding, out_shape.Lp, out_shape.HP,
-                                             ptr(gx), ptr(g_eff), None, stream_ptr(dev)), 'psnd_convtr1d_cl_bwd')
+        with on(dev) as hip:
+            hip.psnd_convtr1d_cl_bwd(g_raw, g_act, act if g_act is not None else None, slope, wb, xa, shape.N, shape.Lp, shape.L, shape.HP, Cip, Cr,
+                                     stride, padding, out_shape.Lp, out_shape.HP, gx, g_eff, None)
             if side is None:
-                g_bias = param_side(stream_ptr(dev))
+                g_bias = param_side(hip)
             else:
                 side.wait_stream(main)                       # the combined gradient is complete on the main stream
-                with torch.cuda.stream(side):
+                with torch.cuda.stream(side), on(dev) as hip_side:
                     gw = torch.empty_like(gw)
                     gv, gg = torch.empty_like(gv), torch.empty_like(gg)
-                    g_bias = param_side(stream_ptr(dev))
+                    g_bias = param_side(hip_side)
                 for t in (g_raw, g_act, g_eff, act, xa, v32, g32, wb):     # allocated on the main stream, still read by the side stream
                     if t is not None:
                         t.record_stream(side)
@@ -859,9 +803,8 @@ def prep_all_convtr(owner, ups):
     for u in ups:
         if not (u.weight_v.is_contiguous() and u.weight_g.is_contiguous() and u.weight_v.dtype == torch.float32):
             raise _lib.PsndError('prep_all_convtr: fp32 contiguous weight_v / weight_g expected')
-    with torch.cuda.device(cache['dev']):
-        check(lib().psnd_convtr1d_prep_multi(ptr(cache['table']), cache['n'], cache['blocks'], stream_ptr(cache['dev'])),
-              'psnd_convtr1d_prep_multi')
+    with on(cache['dev']) as hip:
+        hip.psnd_convtr1d_prep_multi(cache['table'], cache['n'], cache['blocks'])
     return cache['packs']
 
 
@@ -900,9 +843,8 @@ class FanOutCL(torch.autograd.Function):
         pa = (ctypes.c_void_p * max(1, len(ra)))(*[g.data_ptr() for g in ra])
         pb = (ctypes.c_void_p * max(1, len(aa)))(*[g.data_ptr() for g in aa])
         n = (ra or aa)[0].numel()
-        with torch.cuda.device(dev):
-            check(lib().psnd_cl_sum2(pa, len(ra), ptr(out_r) if ra else None, pb, len(aa), ptr(out_a) if aa else None, n, stream_ptr(dev)),
-                  'psnd_cl_sum2')
+        with on(dev) as hip:
+            hip.psnd_cl_sum2(pa, len(ra), out_r if ra else None, pb, len(aa), out_a if aa else None, n)
         return out_r, out_a, None
 
 
@@ -920,9 +862,8 @@ class MeanActCL(torch.autograd.Function):
             _need(r, torch.bfloat16)
         out = torch.empty_like(rs[0])
         ps = [ptr(r) for r in rs] + [None] * (4 - n)
-        with torch.cuda.device(out.device):
-            check(lib().psnd_cl_mean_act_fwd(ps[0], ps[1], ps[2], ps[3], n, float(slope), ptr(out), out.numel(), stream_ptr(out.device)),
-                  'psnd_cl_mean_act_fwd')
+        with on(out.device) as hip:
+            hip.psnd_cl_mean_act_fwd(ps[0], ps[1], ps[2], ps[3], n, float(slope), out, out.numel())
         ctx.n, ctx.slope = n, float(slope)
         ctx.save_for_backward(out)
         return out
@@ -932,9 +873,8 @@ class MeanActCL(torch.autograd.Function):
         (out,) = ctx.saved_tensors
         g = g.contiguous()
         gin = torch.empty_like(out)
-        with torch.cuda.device(out.device):
-            check(lib().psnd_cl_mean_act_bwd(ptr(g), ptr(out), ctx.n, ctx.slope, ptr(gin), out.numel(), stream_ptr(out.device)),
-                  'psnd_cl_mean_act_bwd')
+        with on(out.device) as hip:
+            hip.psnd_cl_mean_act_bwd(g, out, ctx.n, ctx.slope, gin, out.numel())
         return (None,) + (gin,) * ctx.n
 
 
@@ -948,9 +888,8 @@ class PrepPacks(dict):
         if cache is None or cache['wb_done']:
             return
         cache['wb_done'] = True
-        with torch.cuda.device(cache['dev']):
-            check(lib().psnd_conv1d_prep_multi(ptr(cache['table']), cache['n'], cache['blocks'], cache['max_row'], 2, stream_ptr(cache['dev'])),
-                  'psnd_conv1d_prep_multi')
+        with on(cache['dev']) as hip:
+            hip.psnd_conv1d_prep_multi(cache['table'], cache['n'], cache['blocks'], cache['max_row'], 2)
 
 
 def prep_all(owner, convs, defer_backward_packs=False):
@@ -994,9 +933,8 @@ def prep_all(owner, convs, defer_backward_packs=False):
         if not (c.weight_v.is_contiguous() and c.weight_g.is_contiguous() and c.weight_v.dtype == torch.float32):
             raise _lib.PsndError('prep_all: fp32 contiguous weight_v / weight_g expected')
     defer = bool(defer_backward_packs) and torch.is_grad_enabled() and _sw.lab('PSND_PREP_NO_DEFER') != '1'
-    with torch.cuda.device(cache['dev']):
-        check(lib().psnd_conv1d_prep_multi(ptr(cache['table']), cache['n'], cache['blocks'], cache['max_row'], 1 if defer else 3,
-                                           stream_ptr(cache['dev'])), 'psnd_conv1d_prep_multi')
+    with on(cache['dev']) as hip:
+        hip.psnd_conv1d_prep_multi(cache['table'], cache['n'], cache['blocks'], cache['max_row'], 1 if defer else 3)
     cache['wb_done'] = not defer
     cache['packs'].deferred = cache if defer else None
     return cache['packs']
@@ -1045,9 +983,8 @@ class ResBlockCL(torch.autograd.Function):
                 wb = torch.empty((k, Ca, Cb), dtype=torch.bfloat16, device=dev)
                 bp = torch.empty(Cb, dtype=torch.float32, device=dev)
                 b32 = None if b is None else b.detach().contiguous()
-                with torch.cuda.device(dev):
-                    check(lib().psnd_conv1d_prep(ptr(v32), ptr(g32), ptr(b32), Cout, Cin, k, Cb, Ca, ptr(wf), ptr(wb), ptr(bp),
-                                                 stream_ptr(dev)), 'psnd_conv1d_prep')
+                with on(dev) as hip:
+                    hip.psnd_conv1d_prep(v32, g32, b32, Cout, Cin, k, Cb, Ca, wf, wb, bp)
             last = i == n - 1
             inp, slope, has_res = src, (last_act_slope if last else 0.1), role in ('c2', 'r2')
             mk = lambda: torch.empty((shape.N, shape.Lp, Cb), dtype=torch.bfloat16, device=dev)   # noqa: E731
@@ -1074,31 +1011,28 @@ class ResBlockCL(torch.autograd.Function):
         plan = _chain_pairs(plan, Nh * shape.Lp)
 
         def run(h):
-            st = stream_ptr(dev)
             q = lambda t: ptr(_sec(t, h, nsec))                # noqa: E731
-            for e in plan:
-                if isinstance(e, _Chain):
-                    inp1, res0, C, k, pairs = e
-                    arr = (_lib.ChainPair * len(pairs))()
-                    for d, p in zip(arr, pairs):
-                        d.W1, d.bias1, d.act1_slope, d.mid_out = p.wf1.data_ptr(), p.bp1.data_ptr(), float(p.slope1), q(p.mid)
-                        d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wf2.data_ptr(), p.bp2.data_ptr(), p.off1, p.dstep1, p.off2, p.dstep2
-                        # the residual stream BETWEEN the pairs of a chain never leaves the chip (nothing reads it back: the backward
-                        # needs the activated tensors only); the last pair's is the next launch's
-                        d.act2_slope, d.out_raw, d.out_act = float(p.oslope), (q(p.raw) if p is pairs[-1] else None), q(p.act)
-                    check(lib().psnd_conv1d_cl_chain(q(inp1), q(res0), ctypes.addressof(arr), len(pairs), Nh, shape.Lp, shape.L, shape.HP,
-                                                     C, k, st), 'psnd_conv1d_cl_chain')
-                    continue
-                if isinstance(e, _Pair):
-                    inp1, wf1, bp1, slope1, mid, wf2, bp2, res, C, k, off1, dstep1, off2, dstep2, oslope, raw, act = e
-                    check(lib().psnd_conv1d_cl_pair(q(inp1), ptr(wf1), ptr(bp1), None, 1.0, float(slope1), q(mid), ptr(wf2), ptr(bp2),
-                                                    None, 1.0, q(res), Nh, shape.Lp, shape.L, shape.HP, C, k, off1, dstep1, off2, dstep2,
-                                                    float(oslope), q(raw), q(act), st), 'psnd_conv1d_cl_pair')
-                    continue
-                inp, wf, bp, res, Ca, Cb, k, off0, dil, oslope, raw, act = e
-                check(lib().psnd_conv1d_cl(q(inp), None, None, 1.0, ptr(wf), ptr(bp), q(res), None,
-                                           Nh, shape.Lp, shape.L, shape.HP, Ca, Cb, k, off0, dil, float(oslope), 1.0,
-                                           q(raw), q(act), None, st), 'psnd_conv1d_cl')
+            with on(dev) as hip:
+                for e in plan:
+                    if isinstance(e, _Chain):
+                        inp1, res0, C, k, pairs = e
+                        arr = (_lib.ChainPair * len(pairs))()
+                        for d, p in zip(arr, pairs):
+                            d.W1, d.bias1, d.act1_slope, d.mid_out = p.wf1.data_ptr(), p.bp1.data_ptr(), float(p.slope1), q(p.mid)
+                            d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wf2.data_ptr(), p.bp2.data_ptr(), p.off1, p.dstep1, p.off2, p.dstep2
+                            # the residual stream BETWEEN the pairs of a chain never leaves the chip (nothing reads it back: the backward
+                            # needs the activated tensors only); the last pair's is the next launch's
+                            d.act2_slope, d.out_raw, d.out_act = float(p.oslope), (q(p.raw) if p is pairs[-1] else None), q(p.act)
+                        hip.psnd_conv1d_cl_chain(q(inp1), q(res0), ctypes.addressof(arr), len(pairs), Nh, shape.Lp, shape.L, shape.HP, C, k)
+                        continue
+                    if isinstance(e, _Pair):
+                        inp1, wf1, bp1, slope1, mid, wf2, bp2, res, C, k, off1, dstep1, off2, dstep2, oslope, raw, act = e
+                        hip.psnd_conv1d_cl_pair(q(inp1), wf1, bp1, None, 1.0, float(slope1), q(mid), wf2, bp2, None, 1.0, q(res), Nh, shape.Lp, shape.L,
+                                                shape.HP, C, k, off1, dstep1, off2, dstep2, float(oslope), q(raw), q(act))
+                        continue
+                    inp, wf, bp, res, Ca, Cb, k, off0, dil, oslope, raw, act = e
+                    hip.psnd_conv1d_cl(q(inp), None, None, 1.0, wf, bp, q(res), None, Nh, shape.Lp, shape.L, shape.HP, Ca, Cb, k, off0, dil,
+                                       float(oslope), 1.0, q(raw), q(act), None)
 
         with torch.cuda.device(dev):
             _run_sections(dev, nsec, sides, run)
@@ -1153,7 +1087,7 @@ class ResBlockCL(torch.autograd.Function):
         own_launch = []                        # (plan entry, conv): convs whose weight-gradient slabs are written by that entry itself
         pair_bwd = nsec == 1 and not wstreams and not batch and _pair_enabled() and shape.N * shape.Lp <= 8192
         lag = None                             # weight gradient of a pair's first conv, carried to the next pair launch
-        with torch.cuda.device(dev):
+        with on(dev) as hip:                   # (wgrad_batch and finish launch through it; run opens its own: it is also called under a side stream)
             # The gradient a conv receives is  g = g_raw + g_act * leaky'(own activated output).  Only the block's LAST conv gets
             # the two parts from outside and combines them on load; every earlier conv's g is formed in the EPILOGUE of the input-
             # gradient role that produces g_act (mask by the activation, add the residual branch's gradient), so its own backward
@@ -1271,66 +1205,56 @@ class ResBlockCL(torch.autograd.Function):
             used = []
 
             def run(h, entries=None):
-                st = stream_ptr(dev)
                 q = lambda t: ptr(_sec(t, h, nsec))            # noqa: E731
                 main = torch.cuda.current_stream(dev)
-                for e in (plan if entries is None else entries):
-                    if isinstance(e, _Side):                   # a weight gradient on the next side stream, behind what is enqueued so far
-                        sd = wstreams[len(used) % len(wstreams)]
-                        used.append(sd)
-                        ev = torch.cuda.Event()
-                        ev.record(main)
-                        sd.wait_event(ev)
-                        G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e.w
-                        with torch.cuda.stream(sd):
-                            check(lib().psnd_conv1d_cl_wgrad(ptr(G1), ptr(G2), ptr(am), float(slope), ptr(inp), shape.N, shape.Lp, Ca, Cb, k,
-                                                             off0, dil, ptr(gw), ptr(gbp), None, stream_ptr(dev)), 'psnd_conv1d_cl_wgrad')
-                        continue
-                    if isinstance(e, _PB):
-                        G, wb2, m1, m1s, g_h, wb1, m2, m2s, C, k, pad2, dil2, pad1, dil1, gx, gw, gbp, lg = e
-                        if lg is None:                         # the first pair walked: nothing carried yet
-                            lg = _Lag(None, None, 0, 0, None, None, C, k)
-                        check(lib().psnd_conv1d_cl_pair_bwd(ptr(G), ptr(wb2), ptr(m1), m1s, ptr(g_h), ptr(wb1), ptr(m2), m2s, ptr(G), shape.N,
-                                                            shape.Lp, shape.L, shape.HP, C, k, pad2, dil2, pad1, dil1, ptr(gx), ptr(m1), ptr(gw),
-                                                            ptr(gbp), ptr(lg.g), ptr(lg.xa), lg.off0, lg.dstep, ptr(lg.gw), ptr(lg.gbp), st),
-                              'psnd_conv1d_cl_pair_bwd')
-                        continue
-                    if isinstance(e, _PBFlush):
-                        lg = e.lag
-                        check(lib().psnd_conv1d_cl_pair_bwd(None, None, None, 1.0, None, None, None, 1.0, None, shape.N, shape.Lp, shape.L,
-                                                            shape.HP, lg.C, lg.k, 0, 1, 0, 1, None, None, None, None, ptr(lg.g), ptr(lg.xa),
-                                                            lg.off0, lg.dstep, ptr(lg.gw), ptr(lg.gbp), st), 'psnd_conv1d_cl_pair_bwd')
-                        continue
-                    if isinstance(e, _ChainB):
-                        arr = (_lib.ChainPair * len(e.pairs))()
-                        for d, p in zip(arr, e.pairs):
-                            d.W1, d.bias1, d.act1_slope, d.mid_out = p.wb2.data_ptr(), None, 1.0, p.g_h.data_ptr()
-                            d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wb1.data_ptr(), None, p.off1, p.dstep1, p.off2, p.dstep2
-                            d.act2_slope, d.out_raw, d.out_act = 1.0, p.gx.data_ptr(), None
-                            d.M1, d.M2, d.m1_slope, d.m2_slope = p.m1.data_ptr(), p.m2.data_ptr(), p.m1s, p.m2s
-                        p0 = e.pairs[0]
-                        check(lib().psnd_conv1d_cl_chain(ptr(p0.G), ptr(p0.G), ctypes.addressof(arr), len(e.pairs), shape.N, shape.Lp, shape.L,
-                                                         shape.HP, p0.C, p0.k, st), 'psnd_conv1d_cl_chain')
-                        continue
-                    if isinstance(e, _PairB):
-                        G, wb2, m1, m1s, g_h, wb1, m2, m2s, res, C, k, off1, dstep1, off2, dstep2, gx, _ = e
-                        check(lib().psnd_conv1d_cl_pair(ptr(G), ptr(wb2), None, ptr(m1), m1s, 1.0, ptr(g_h), ptr(wb1), None, ptr(m2), m2s,
-                                                        ptr(res), shape.N, shape.Lp, shape.L, shape.HP, C, k, off1, dstep1, off2, dstep2, 1.0,
-                                                        ptr(gx), None, st), 'psnd_conv1d_cl_pair')
-                        continue
-                    if isinstance(e, _W):
-                        G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e
-                        check(lib().psnd_conv1d_cl_wgrad(q(G1), q(G2), q(am), float(slope), q(inp), Nh, shape.Lp, Ca, Cb, k, off0, dil,
-                                                         ptr(gw[h * S:(h + 1) * S]), ptr(gbp[h * S:(h + 1) * S]), None, st),
-                              'psnd_conv1d_cl_wgrad')
-                    else:
-                        G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask, ep_slope, ep_res, gw, gbp, S = e
-                        check(lib().psnd_conv1d_cl_bwd(q(G1), q(G2), q(am), float(slope), ptr(wb), q(inp), Nh, shape.Lp, shape.L,
-                                                       shape.HP, Ca, Cb, k, pad, dil, q(gx), q(g_out), q(ep_mask), ep_slope, q(ep_res),
-                                                       ptr(gw[h * S:(h + 1) * S]), ptr(gbp[h * S:(h + 1) * S]), st),
-                              'psnd_conv1d_cl_bwd')
+                with on(dev) as hip:
+                    for e in (plan if entries is None else entries):
+                        if isinstance(e, _Side):                   # a weight gradient on the next side stream, behind what is enqueued so far
+                            sd = wstreams[len(used) % len(wstreams)]
+                            used.append(sd)
+                            ev = torch.cuda.Event()
+                            ev.record(main)
+                            sd.wait_event(ev)
+                            G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e.w
+                            with torch.cuda.stream(sd), on(dev) as hip_side:
+                                hip_side.psnd_conv1d_cl_wgrad(G1, G2, am, float(slope), inp, shape.N, shape.Lp, Ca, Cb, k, off0, dil, gw, gbp, None)
+                            continue
+                        if isinstance(e, _PB):
+                            G, wb2, m1, m1s, g_h, wb1, m2, m2s, C, k, pad2, dil2, pad1, dil1, gx, gw, gbp, lg = e
+                            if lg is None:                         # the first pair walked: nothing carried yet
+                                lg = _Lag(None, None, 0, 0, None, None, C, k)
+                            hip.psnd_conv1d_cl_pair_bwd(G, wb2, m1, m1s, g_h, wb1, m2, m2s, G, shape.N, shape.Lp, shape.L, shape.HP, C, k, pad2, dil2,
+                                                        pad1, dil1, gx, m1, gw, gbp, lg.g, lg.xa, lg.off0, lg.dstep, lg.gw, lg.gbp)
+                            continue
+                        if isinstance(e, _PBFlush):
+                            lg = e.lag
+                            hip.psnd_conv1d_cl_pair_bwd(None, None, None, 1.0, None, None, None, 1.0, None, shape.N, shape.Lp, shape.L, shape.HP, lg.C,
+                                                        lg.k, 0, 1, 0, 1, None, None, None, None, lg.g, lg.xa, lg.off0, lg.dstep, lg.gw, lg.gbp)
+                            continue
+                        if isinstance(e, _ChainB):
+                            arr = (_lib.ChainPair * len(e.pairs))()
+                            for d, p in zip(arr, e.pairs):
+                                d.W1, d.bias1, d.act1_slope, d.mid_out = p.wb2.data_ptr(), None, 1.0, p.g_h.data_ptr()
+                                d.W2, d.bias2, d.off1, d.dstep1, d.off2, d.dstep2 = p.wb1.data_ptr(), None, p.off1, p.dstep1, p.off2, p.dstep2
+                                d.act2_slope, d.out_raw, d.out_act = 1.0, p.gx.data_ptr(), None
+                                d.M1, d.M2, d.m1_slope, d.m2_slope = p.m1.data_ptr(), p.m2.data_ptr(), p.m1s, p.m2s
+                            p0 = e.pairs[0]
+                            hip.psnd_conv1d_cl_chain(p0.G, p0.G, ctypes.addressof(arr), len(e.pairs), shape.N, shape.Lp, shape.L, shape.HP, p0.C, p0.k)
+                            continue
+                        if isinstance(e, _PairB):
+                            G, wb2, m1, m1s, g_h, wb1, m2, m2s, res, C, k, off1, dstep1, off2, dstep2, gx, _ = e
+                            hip.psnd_conv1d_cl_pair(G, wb2, None, m1, m1s, 1.0, g_h, wb1, None, m2, m2s, res, shape.N, shape.Lp, shape.L, shape.HP, C, k,
+                                                    off1, dstep1, off2, dstep2, 1.0, gx, None)
+                            continue
+                        if isinstance(e, _W):
+                            G1, G2, am, slope, inp, Ca, Cb, k, off0, dil, gw, gbp, S = e
+                            hip.psnd_conv1d_cl_wgrad(q(G1), q(G2), q(am), float(slope), q(inp), Nh, shape.Lp, Ca, Cb, k, off0, dil, gw[h * S:(h + 1) * S],
+                                                     gbp[h * S:(h + 1) * S], None)
+                        else:
+                            G1, G2, am, slope, wb, inp, Ca, Cb, k, pad, dil, gx, g_out, ep_mask, ep_slope, ep_res, gw, gbp, S = e
+                            hip.psnd_conv1d_cl_bwd(q(G1), q(G2), q(am), float(slope), wb, q(inp), Nh, shape.Lp, shape.L, shape.HP, Ca, Cb, k, pad, dil,
+                                                   q(gx), q(g_out), q(ep_mask), ep_slope, q(ep_res), gw[h * S:(h + 1) * S], gbp[h * S:(h + 1) * S])
 
-            st = stream_ptr(dev)
             handed = set()
 
             def wgrad_batch(part):
@@ -1350,7 +1274,7 @@ class ResBlockCL(torch.autograd.Function):
                         w = slabs(b.conv, b.G, None, None, b.inp, Sb)
                         d.g, d.xa, d.gw_part, d.gbias_part, d.off0, d.dstep = b.G.data_ptr(), b.inp.data_ptr(), w.gw.data_ptr(), w.gbp.data_ptr(), b.off0, b.dstep
                         d.Ca, d.Cb, d.k, d.splits = w.Ca, w.Cb, w.k, Sb
-                    check(lib().psnd_conv1d_cl_wgrad_multi(ctypes.addressof(arr), len(sub), shape.N, shape.Lp, st), 'psnd_conv1d_cl_wgrad_multi')
+                    hip.psnd_conv1d_cl_wgrad_multi(ctypes.addressof(arr), len(sub), shape.N, shape.Lp)
 
             def finish(convs):
                 """weight-norm backward of these convs (their slabs are complete on this stream), then the hand-over of what went straight
@@ -1359,7 +1283,7 @@ class ResBlockCL(torch.autograd.Function):
                 for j0 in range(0, len(ds), _lib.DEFINES['PSND_WNORM_MAX']):
                     chunk = ds[j0:j0 + _lib.DEFINES['PSND_WNORM_MAX']]
                     arr = (_lib.WnormDesc * len(chunk))(*chunk)
-                    check(lib().psnd_conv1d_wnorm_bwd_multi(ctypes.addressof(arr), len(chunk), st), 'psnd_conv1d_wnorm_bwd_multi')
+                    hip.psnd_conv1d_wnorm_bwd_multi(ctypes.addressof(arr), len(chunk))
                 out = []
                 for ci in convs:
                     for ent in early.get(ci, ()):

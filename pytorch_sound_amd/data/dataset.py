@@ -249,7 +249,7 @@ class RaggedBatch:
     def to_device(self, device, want_mask: bool = False, multiple: int = 1):
         """(N, Tmax) zero-padded batch (+ mask) in HBM via psnd_pad_collate, enqueued on the current stream of `device`.
         ``multiple`` rounds Tmax up (e.g. to the hop size) so downstream shapes repeat and hipGraphs are reused."""
-        from pytorch_sound_amd._lib import lib, check, ptr, stream_ptr
+        from pytorch_sound_amd._lib import on
         N = len(self)
         Tmax = int(self.lens.max())
         Tmax = (Tmax + multiple - 1) // multiple * multiple
@@ -257,9 +257,8 @@ class RaggedBatch:
         meta = torch.stack([self.offs, self.lens]).to(device, non_blocking=True)
         out = torch.empty((N, Tmax), dtype=torch.float32, device=device)
         mask = torch.empty((N, Tmax), dtype=torch.float32, device=device) if want_mask else None
-        with torch.cuda.device(device):
-            check(lib().psnd_pad_collate(ptr(flat), ptr(meta[0]), ptr(meta[1]), N, Tmax, ptr(out), ptr(mask), stream_ptr(device)),
-                  'psnd_pad_collate')
+        with on(device) as hip:
+            hip.psnd_pad_collate(flat, meta[0], meta[1], N, Tmax, out, mask)
         return (out, mask) if want_mask else out
 
 

@@ -226,12 +226,11 @@ class FlatGradReducer:
         if c is None:
             c = b['comm'] = torch.empty(flat.numel(), dtype=torch.bfloat16, device=flat.device)
         if flat.is_cuda:
-            from ._lib import lib, check, ptr, stream_ptr
-            with torch.cuda.device(flat.device):
-                st = stream_ptr(flat.device)
-                check(lib().psnd_grad_pack_bf16(ptr(flat), ptr(c), flat.numel(), 1.0, st), 'psnd_grad_pack_bf16')
+            from ._lib import on
+            with on(flat.device) as hip:
+                hip.psnd_grad_pack_bf16(flat, c, flat.numel(), 1.0)
                 dist.all_reduce(c, op=dist.ReduceOp.SUM)         # stream-ordered: this stream waits for RCCL's, the host does not
-                check(lib().psnd_grad_unpack_bf16(ptr(c), ptr(flat), flat.numel(), 1.0, st), 'psnd_grad_unpack_bf16')
+                hip.psnd_grad_unpack_bf16(c, flat, flat.numel(), 1.0)
         else:                                                    # the gloo tests on CPU tensors
             c.copy_(flat)
             dist.all_reduce(c, op=dist.ReduceOp.SUM)
@@ -485,8 +484,9 @@ class FlatGradReducer:
             if mode == 'capture':
                 self._cap_works.append(self._reduce(b))
             elif mode == 'events':
-                from ._lib import lib, check
-                check(lib().psnd_event_record_external(self._events[i], rel.cuda_stream), 'psnd_event_record_external')   # (events mode: HIP tensors only)
+                from ._lib import on
+                with on(b['flat'].device) as hip:            # (events mode: HIP tensors only; `rel` is the current stream here)
+                    hip.psnd_event_record_external(self._events[i])
         self.launch_log.append(i)
         self.handover_log.append((i, self._in_deliver))
         self.emit_log.append((i, self._arrived))
@@ -526,6 +526,7 @@ class FlatGradReducer:
         self.release_marks = []
         with torch.cuda.stream(self._side):
             for i, b in enumerate(self.buckets):
+                # (not a launch: the header puts this entry point's stream first, so it is not one of the launcher's)
                 check(lib().psnd_stream_wait_event(self._side.cuda_stream, self._events[i]), 'psnd_stream_wait_event')
                 if time_marks:
                     m = torch.cuda.Event(enable_timing=True)

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import PsndError  # noqa: F401
-from ._lib import lib, check, ptr, stream_ptr, FRAMING_CENTER, FRAMING_HIFIGAN, FRAMING_NONE, LOG_NONE, LOG_E, LOG_10  # noqa: F401
+from ._lib import lib, check, ptr, stream_ptr, on, FRAMING_CENTER, FRAMING_HIFIGAN, FRAMING_NONE, LOG_NONE, LOG_E, LOG_10  # noqa: F401
 
 _INF = float('inf')
 
@@ -82,6 +82,46 @@ def frame_count(T, n_fft, hop, framing=FRAMING_CENTER):
     return _lib.frame_count(T, n_fft, hop, framing)
 
 
+def _out_tensor(out, shape, device, what, ok=True):
+    """the output tensor of a launch: a new one, or the caller's `out` (a persistent buffer) once it is seen to be what the kernel writes"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not ok or tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != device or not out.is_contiguous():
+        raise _lib.PsndError('%s must be a contiguous fp32 (%d, %d, %d) tensor on %s' % ((what,) + shape + (device,)))
+    return out
+
+
+def _timed(events, N, launch, *args):
+    """launch(*args); with `events` a list (STFT_FWD_EVENTS / STFT_NFK_EVENTS) between a pair of timing events recorded on the launch
+    stream directly around it - not inside a hipGraph capture"""
+    if events is None or torch.cuda.is_current_stream_capturing():
+        return launch(*args)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch(*args)
+    e1.record()
+    events.append((e0, e1, N))
+
+
+def _scratch(nbytes, device):
+    """(scratch tensor, its size in bytes) as the entry points with a scratch take them"""
+    scratch = torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=device)
+    return scratch, scratch.numel() * 4
+
+
+_MR_ENTRY = {'psnd_stft_fwd': 'psnd_stft_mr_fwd', 'psnd_stft_bwd': 'psnd_stft_mr_bwd', 'psnd_istft': 'psnd_istft_mr',
+             'psnd_istft_reim': 'psnd_istft_reim_mr'}
+
+
+def _plan_launch(hip, name, plan, n_fft, mr_scratch=None):
+    """the two plan kinds behind one name: (launch, plan arguments, scratch arguments) of entry point `name` for this plan.  A power-of-two
+    plan is passed alone and needs no scratch; the mixed-radix twin takes the plan with its size and, where it works through a scratch,
+    the `_scratch` that `mr_scratch()` allocates."""
+    if stft_plan_kind(plan, n_fft) != PLAN_MR:
+        return getattr(hip, name), (plan,), ()
+    return getattr(hip, _MR_ENTRY[name]), (plan, _plan_bytes(plan)), mr_scratch() if mr_scratch else ()
+
+
 def stft_forward(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0,
                  want_mag=True, want_phase=False, want_reim=False, out_mag=None):
     """wav (N,T) fp32 cuda -> dict of requested (N,K,F) tensors.  out_mag: a caller-owned (N,K,F) fp32 tensor the magnitude is written
@@ -96,27 +136,16 @@ def stft_forward(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0,
     F = frame_count(T, n_fft, hop, framing)
     K = n_fft // 2 + 1
     mk = lambda: torch.empty((N, K, F), dtype=torch.float32, device=wav.device)  # noqa: E731
-    if out_mag is not None and (not want_mag or tuple(out_mag.shape) != (N, K, F) or out_mag.dtype != torch.float32
-                                or out_mag.device != wav.device or not out_mag.is_contiguous()):
-        raise _lib.PsndError('stft_forward: out_mag must be a contiguous fp32 (%d, %d, %d) tensor on %s' % (N, K, F, wav.device))
-    mag = (out_mag if out_mag is not None else mk()) if want_mag else None
+    if want_mag or out_mag is not None:
+        mag = _out_tensor(out_mag, (N, K, F), wav.device, 'stft_forward: out_mag', ok=want_mag)
+    else:
+        mag = None
     phase = mk() if want_phase else None
     re = mk() if want_reim else None
     im = mk() if want_reim else None
-    ev = STFT_FWD_EVENTS if not torch.cuda.is_current_stream_capturing() else None   # no timing events inside a hipGraph capture
-    with torch.cuda.device(wav.device):
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if stft_plan_kind(plan, n_fft) == PLAN_MR:
-            check(lib().psnd_stft_mr_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), _plan_bytes(plan), float(mag_eps),
-                                         ptr(mag), ptr(phase), ptr(re), ptr(im), stream_ptr(wav.device)), 'psnd_stft_mr_fwd')
-        else:
-            check(lib().psnd_stft_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps),
-                                      ptr(mag), ptr(phase), ptr(re), ptr(im), stream_ptr(wav.device)), 'psnd_stft_fwd')
-        if ev is not None:
-            e1.record()
-            ev.append((e0, e1, N))
+    with on(wav.device) as hip:
+        launch, plan_args, _ = _plan_launch(hip, 'psnd_stft_fwd', plan, n_fft)
+        _timed(STFT_FWD_EVENTS, N, launch, wav, N, T, n_fft, hop, framing, *plan_args, float(mag_eps), mag, phase, re, im)
     return {'mag': mag, 'phase': phase, 're': re, 'im': im}
 
 
@@ -132,20 +161,9 @@ def stft_mag_nfk(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0, out
     N, T = wav.shape
     F = frame_count(T, n_fft, hop, framing)
     K = n_fft // 2 + 1
-    if out is None:
-        out = torch.empty((N, F, K), dtype=torch.float32, device=wav.device)
-    elif tuple(out.shape) != (N, F, K) or out.dtype != torch.float32 or out.device != wav.device or not out.is_contiguous():
-        raise _lib.PsndError('stft_mag_nfk: out must be a contiguous fp32 (%d, %d, %d) tensor on %s' % (N, F, K, wav.device))
-    ev = STFT_NFK_EVENTS if not torch.cuda.is_current_stream_capturing() else None
-    with torch.cuda.device(wav.device):
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(lib().psnd_stft_mag_nfk(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps), ptr(out), stream_ptr(wav.device)),
-              'psnd_stft_mag_nfk')
-        if ev is not None:
-            e1.record()
-            ev.append((e0, e1, N))
+    out = _out_tensor(out, (N, F, K), wav.device, 'stft_mag_nfk: out')
+    with on(wav.device) as hip:
+        _timed(STFT_NFK_EVENTS, N, hip.psnd_stft_mag_nfk, wav, N, T, n_fft, hop, framing, plan, float(mag_eps), out)
     return out
 
 
@@ -158,18 +176,11 @@ def stft_backward(wav, n_fft, hop, plan, framing=FRAMING_CENTER, mag_eps=0.0, gm
         if g is not None:
             _need_cuda(g, 'grad')
     gwav = torch.empty_like(wav)
-    with torch.cuda.device(wav.device):
-        if stft_plan_kind(plan, n_fft) == PLAN_MR:
-            # two launches: the windowed frame gradients go through a scratch, every sample gathers its frames in a fixed order
-            nb = int(lib().psnd_stft_mr_bwd_scratch_bytes(N, T, n_fft, hop, framing))
-            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=wav.device)
-            check(lib().psnd_stft_mr_bwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), _plan_bytes(plan), float(mag_eps),
-                                         ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(scratch), scratch.numel() * 4, ptr(gwav),
-                                         stream_ptr(wav.device)), 'psnd_stft_mr_bwd')
-            return gwav
-        check(lib().psnd_stft_bwd(ptr(wav), N, T, n_fft, hop, framing, ptr(plan), float(mag_eps),
-                                  ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gwav), stream_ptr(wav.device)),
-              'psnd_stft_bwd')
+    with on(wav.device) as hip:
+        # mixed radix: two launches, the windowed frame gradients go through a scratch, every sample gathers its frames in a fixed order
+        launch, plan_args, scratch = _plan_launch(hip, 'psnd_stft_bwd', plan, n_fft, lambda: _scratch(
+            lib().psnd_stft_mr_bwd_scratch_bytes(N, T, n_fft, hop, framing), wav.device))
+        launch(wav, N, T, n_fft, hop, framing, *plan_args, float(mag_eps), *gs, *scratch, gwav)
     return gwav
 
 
@@ -186,15 +197,10 @@ def mel_forward(mag, mel_plan_t, M, log_kind=LOG_E, log_offset=0.0, pre_clamp_mi
     mag = mag.contiguous()
     N, K, F = mag.shape
     lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
-    if out is not None and (tuple(out.shape) != (N, M, F) or out.dtype != torch.float32 or out.device != mag.device
-                            or not out.is_contiguous()):
-        raise _lib.PsndError('mel_forward: out must be a contiguous fp32 (%d, %d, %d) tensor on %s' % (N, M, F, mag.device))
-    if out is None:
-        out = torch.empty((N, M, F), dtype=torch.float32, device=mag.device)
+    out = _out_tensor(out, (N, M, F), mag.device, 'mel_forward: out')
     lin = torch.empty_like(out) if want_lin else None
-    with torch.cuda.device(mag.device):
-        check(lib().psnd_mel_fwd(ptr(mag), N, F, M, K, ptr(mel_plan_t), log_kind, float(log_offset), pre, lo, hi,
-                                 ptr(out), ptr(lin), stream_ptr(mag.device)), 'psnd_mel_fwd')
+    with on(mag.device) as hip:
+        hip.psnd_mel_fwd(mag, N, F, M, K, mel_plan_t, log_kind, float(log_offset), pre, lo, hi, out, lin)
     return out, lin
 
 
@@ -205,15 +211,10 @@ def mel_forward_nfk(mag_nfk, mel_plan_t, M, log_kind=LOG_E, log_offset=0.0, pre_
     mag_nfk = mag_nfk.contiguous()
     N, F, K = mag_nfk.shape
     lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
-    if out is not None and (tuple(out.shape) != (N, M, F) or out.dtype != torch.float32 or out.device != mag_nfk.device
-                            or not out.is_contiguous()):
-        raise _lib.PsndError('mel_forward_nfk: out must be a contiguous fp32 (%d, %d, %d) tensor on %s' % (N, M, F, mag_nfk.device))
-    if out is None:
-        out = torch.empty((N, M, F), dtype=torch.float32, device=mag_nfk.device)
+    out = _out_tensor(out, (N, M, F), mag_nfk.device, 'mel_forward_nfk: out')
     lin = torch.empty_like(out) if want_lin else None
-    with torch.cuda.device(mag_nfk.device):
-        check(lib().psnd_mel_fwd_nfk(ptr(mag_nfk), N, F, M, K, ptr(mel_plan_t), log_kind, float(log_offset), pre, lo, hi,
-                                     ptr(out), ptr(lin), stream_ptr(mag_nfk.device)), 'psnd_mel_fwd_nfk')
+    with on(mag_nfk.device) as hip:
+        hip.psnd_mel_fwd_nfk(mag_nfk, N, F, M, K, mel_plan_t, log_kind, float(log_offset), pre, lo, hi, out, lin)
     return out, lin
 
 
@@ -224,9 +225,8 @@ def mel_backward_nfk(gout, mel_lin, mel_plan_t, K, log_kind=LOG_E, log_offset=0.
     N, M, F = gout.shape
     lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
     gmag = torch.empty((N, F, K), dtype=torch.float32, device=gout.device)
-    with torch.cuda.device(gout.device):
-        check(lib().psnd_mel_bwd_nfk(ptr(gout), ptr(mel_lin), N, F, M, K, ptr(mel_plan_t), log_kind, float(log_offset), pre, lo, hi,
-                                     ptr(gmag), stream_ptr(gout.device)), 'psnd_mel_bwd_nfk')
+    with on(gout.device) as hip:
+        hip.psnd_mel_bwd_nfk(gout, mel_lin, N, F, M, K, mel_plan_t, log_kind, float(log_offset), pre, lo, hi, gmag)
     return gmag
 
 
@@ -264,10 +264,8 @@ def logmel_forward(wav, n_fft, hop, stft_plan_t, mel_plan_t, M, framing=FRAMING_
     F = frame_count(T, n_fft, hop, framing)
     lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
     out = torch.empty((N, M, max(F, 0)), dtype=torch.float32, device=wav.device)
-    with torch.cuda.device(wav.device):
-        check(lib().psnd_logmel_fwd(ptr(wav), N, T, n_fft, hop, framing, ptr(stft_plan_t), float(mag_eps), M,
-                                    ptr(mel_plan_t), log_kind, float(log_offset), pre, lo, hi, ptr(out),
-                                    stream_ptr(wav.device)), 'psnd_logmel_fwd')
+    with on(wav.device) as hip:
+        hip.psnd_logmel_fwd(wav, N, T, n_fft, hop, framing, stft_plan_t, float(mag_eps), M, mel_plan_t, log_kind, float(log_offset), pre, lo, hi, out)
     return out
 
 
@@ -278,9 +276,8 @@ def mel_backward(gout, mel_lin, mel_plan_t, K, log_kind=LOG_E, log_offset=0.0, p
     N, M, F = gout.shape
     lo, hi, pre = _clamp_args(clamp_lo, clamp_hi, pre_clamp_min)
     gmag = torch.empty((N, K, F), dtype=torch.float32, device=gout.device)
-    with torch.cuda.device(gout.device):
-        check(lib().psnd_mel_bwd(ptr(gout), ptr(mel_lin), N, F, M, K, ptr(mel_plan_t), log_kind, float(log_offset),
-                                 pre, lo, hi, ptr(gmag), stream_ptr(gout.device)), 'psnd_mel_bwd')
+    with on(gout.device) as hip:
+        hip.psnd_mel_bwd(gout, mel_lin, N, F, M, K, mel_plan_t, log_kind, float(log_offset), pre, lo, hi, gmag)
     return gmag
 
 
@@ -354,9 +351,8 @@ class StftPolar(torch.autograd.Function):
         gphase = gphase.contiguous()
         gmag = None if gmag is None else gmag.contiguous()
         gre, gim = torch.empty_like(mag), torch.empty_like(mag)
-        with torch.cuda.device(mag.device):
-            check(lib().psnd_polar_bwd(ptr(gmag), ptr(gphase), ptr(mag), ptr(phase), mag.numel(), ptr(gre), ptr(gim),
-                                       stream_ptr(mag.device)), 'psnd_polar_bwd')
+        with on(mag.device) as hip:
+            hip.psnd_polar_bwd(gmag, gphase, mag, phase, mag.numel(), gre, gim)
         return stft_backward(wav, n_fft, hop, plan, framing, 0.0, gre=gre, gim=gim), None, None, None, None
 
 
@@ -395,15 +391,10 @@ def istft_forward(magnitude, phase, n_fft, hop, plan, eps=1e-9):
         raise _lib.PsndError('istft: expected (N, %d, F) magnitude and phase, got %s / %s'
                              % (n_fft // 2 + 1, tuple(magnitude.shape), tuple(phase.shape)))
     out = torch.empty((N, max((F - 1) * hop, 0)), dtype=torch.float32, device=magnitude.device)
-    with torch.cuda.device(magnitude.device):
-        if stft_plan_kind(plan, n_fft) == PLAN_MR:
-            nb = int(lib().psnd_istft_mr_scratch_bytes(N, F, n_fft))
-            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=magnitude.device)
-            check(lib().psnd_istft_mr(ptr(magnitude), ptr(phase), N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
-                                      ptr(scratch), scratch.numel() * 4, ptr(out), stream_ptr(magnitude.device)), 'psnd_istft_mr')
-            return out
-        check(lib().psnd_istft(ptr(magnitude), ptr(phase), N, F, n_fft, hop, ptr(plan), float(eps), ptr(out),
-                               stream_ptr(magnitude.device)), 'psnd_istft')
+    with on(magnitude.device) as hip:
+        launch, plan_args, scratch = _plan_launch(hip, 'psnd_istft', plan, n_fft, lambda: _scratch(
+            lib().psnd_istft_mr_scratch_bytes(N, F, n_fft), magnitude.device))
+        launch(magnitude, phase, N, F, n_fft, hop, *plan_args, float(eps), *scratch, out)
     return out
 
 
@@ -502,15 +493,10 @@ def istft_reim_forward(re, im, mask, mask_kind, n_fft, hop, plan, eps=1e-9):
     re, im, mask = _reim_args(re, im, mask, mask_kind, n_fft)
     N, _, F = re.shape
     out = torch.empty((N, max((F - 1) * hop, 0)), dtype=torch.float32, device=re.device)
-    with torch.cuda.device(re.device):
-        if stft_plan_kind(plan, n_fft) == PLAN_MR:
-            nb = int(lib().psnd_istft_mr_scratch_bytes(N, F, n_fft))
-            scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=re.device)
-            check(lib().psnd_istft_reim_mr(ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
-                                           ptr(scratch), scratch.numel() * 4, ptr(out), stream_ptr(re.device)), 'psnd_istft_reim_mr')
-            return out
-        check(lib().psnd_istft_reim(ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), float(eps), ptr(out),
-                                    stream_ptr(re.device)), 'psnd_istft_reim')
+    with on(re.device) as hip:
+        launch, plan_args, scratch = _plan_launch(hip, 'psnd_istft_reim', plan, n_fft, lambda: _scratch(
+            lib().psnd_istft_mr_scratch_bytes(N, F, n_fft), re.device))
+        launch(re, im, mask, mask_kind, N, F, n_fft, hop, *plan_args, float(eps), *scratch, out)
     return out
 
 
@@ -530,12 +516,9 @@ def istft_reim_backward(g, re, im, mask, mask_kind, n_fft, hop, plan, eps=1e-9, 
     g_mask = mk(re) if want_mask else None
     if not want_reim and not want_mask:
         return None, None, None
-    nb = int(lib().psnd_istft_reim_bwd_scratch_bytes(N, F, n_fft))
-    scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=re.device)
-    with torch.cuda.device(re.device):
-        check(lib().psnd_istft_reim_bwd(ptr(g), ptr(re), ptr(im), ptr(mask), mask_kind, N, F, n_fft, hop, ptr(plan), _plan_bytes(plan), float(eps),
-                                        ptr(scratch), scratch.numel() * 4, ptr(g_re), ptr(g_im), ptr(g_mask), stream_ptr(re.device)),
-              'psnd_istft_reim_bwd')
+    scratch = _scratch(lib().psnd_istft_reim_bwd_scratch_bytes(N, F, n_fft), re.device)
+    with on(re.device) as hip:      # one entry point for both plan kinds
+        hip.psnd_istft_reim_bwd(g, re, im, mask, mask_kind, N, F, n_fft, hop, plan, _plan_bytes(plan), float(eps), *scratch, g_re, g_im, g_mask)
     return g_re, g_im, g_mask
 
 
@@ -639,14 +622,14 @@ def _dropout_device(device):
 def dropout_seed(seed, call=0, device=None):
     """(re)start the dropout stream of `device` at {seed, call}: a one-thread kernel on the current stream, no synchronisation"""
     device = _dropout_device(device)
-    with torch.cuda.device(device):
+    with on(device) as hip:
         st = _DROPOUT_STATE.get(device.index)
         if st is None:
             if torch.cuda.is_current_stream_capturing():
                 raise PsndError('dropout on %s: no dropout state yet and a stream capture is under way (the state would live in the graph\'s '
                                 'memory) - call pytorch_sound_amd.kernels.dropout_seed(seed) before the capture' % device)
             st = _DROPOUT_STATE[device.index] = torch.empty(2, dtype=torch.int64, device=device)
-        check(lib().psnd_rng_seed(ptr(st), int(seed) & _U64, int(call) & _U64, stream_ptr(device)), 'psnd_rng_seed')
+        hip.psnd_rng_seed(st, int(seed) & _U64, int(call) & _U64)
     return st
 
 
@@ -693,17 +676,14 @@ class GroupNorm1(torch.autograd.Function):
         g32, b32 = gamma.detach().contiguous(), beta.detach().contiguous()
         key = None
         ctx.drop = None if drop is None else dropout_threshold(drop)
-        with torch.cuda.device(x.device):
+        with on(x.device) as hip:
             if ctx.drop is None:
-                check(lib().psnd_groupnorm1_fwd(ptr(x), ptr(res), ptr(g32), ptr(b32), N, C, T, float(eps), int(relu), ptr(y),
-                                                ptr(stats), ptr(ws), stream_ptr(x.device)), 'psnd_groupnorm1_fwd')
+                hip.psnd_groupnorm1_fwd(x, res, g32, b32, N, C, T, float(eps), int(relu), y, stats, ws)
             else:
                 state = _dropout_state_tensor(x.device)
                 key = torch.empty(2, dtype=torch.int64, device=x.device)           # this application's {seed, call}: backward reads it again
-                check(lib().psnd_rng_next(ptr(state), ptr(key), stream_ptr(x.device)), 'psnd_rng_next')
-                check(lib().psnd_groupnorm1_drop_fwd(ptr(x), ptr(res), ptr(g32), ptr(b32), N, C, T, float(eps), int(relu), ptr(y),
-                                                     ptr(stats), ptr(ws), ptr(key), ctx.drop[0], ctx.drop[1], stream_ptr(x.device)),
-                      'psnd_groupnorm1_drop_fwd')
+                hip.psnd_rng_next(state, key)
+                hip.psnd_groupnorm1_drop_fwd(x, res, g32, b32, N, C, T, float(eps), int(relu), y, stats, ws, key, ctx.drop[0], ctx.drop[1])
         ctx.relu, ctx.has_res = bool(relu), res is not None
         ctx.save_for_backward(x, res, g32, y if relu else None, stats, key)
         return y
@@ -720,16 +700,13 @@ class GroupNorm1(torch.autograd.Function):
         if ctx.drop is not None:
             # two gradients: the sum's (the residual's) and, masked and scaled, x's; the residual's is written only when somebody takes it
             gres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[1]) else None
-            with torch.cuda.device(x.device):
-                check(lib().psnd_groupnorm1_drop_bwd(ptr(gy), ptr(x), ptr(res), ptr(g32), ptr(y), ptr(stats), N, C, T, int(ctx.relu),
-                                                     ptr(gx), ptr(gres), ptr(gg), ptr(gb), ptr(ws), ptr(key), ctx.drop[0], ctx.drop[1],
-                                                     stream_ptr(x.device)), 'psnd_groupnorm1_drop_bwd')
+            with on(x.device) as hip:
+                hip.psnd_groupnorm1_drop_bwd(gy, x, res, g32, y, stats, N, C, T, int(ctx.relu), gx, gres, gg, gb, ws, key, ctx.drop[0], ctx.drop[1])
             if ctx.link is not None and gres is not None and ctx.link.offer(gres):
                 return gx, None, gg, gb, None, None, None, None
             return gx, gres, gg, gb, None, None, None, None
-        with torch.cuda.device(x.device):
-            check(lib().psnd_groupnorm1_bwd(ptr(gy), ptr(x), ptr(res), ptr(g32), ptr(y), ptr(stats), N, C, T, int(ctx.relu),
-                                            ptr(gx), ptr(gg), ptr(gb), ptr(ws), stream_ptr(x.device)), 'psnd_groupnorm1_bwd')
+        with on(x.device) as hip:
+            hip.psnd_groupnorm1_bwd(gy, x, res, g32, y, stats, N, C, T, int(ctx.relu), gx, gg, gb, ws)
         if ctx.link is not None and ctx.needs_input_grad[1] and ctx.link.offer(gx):
             # the residual's gradient travels with the link: the first projection of the branch adds it in its input-gradient GEMM
             return gx, None, gg, gb, None, None, None, None
@@ -749,9 +726,8 @@ class SoftmaxKeys(torch.autograd.Function):
         else:
             att = scores.contiguous().clone()
         B, T, _ = att.shape
-        with torch.cuda.device(att.device):
-            check(lib().psnd_softmax_keys_fwd(ptr(att), ptr(mask_u8), B, T, float(scale), stream_ptr(att.device)),
-                  'psnd_softmax_keys_fwd')
+        with on(att.device) as hip:
+            hip.psnd_softmax_keys_fwd(att, mask_u8, B, T, float(scale))
         ctx.scale = float(scale)
         ctx.save_for_backward(att)
         return att
@@ -762,9 +738,8 @@ class SoftmaxKeys(torch.autograd.Function):
         gatt = gatt.contiguous()
         B, T, _ = att.shape
         gs = torch.empty_like(att)
-        with torch.cuda.device(att.device):
-            check(lib().psnd_softmax_keys_bwd(ptr(att), ptr(gatt), B, T, ctx.scale, ptr(gs), stream_ptr(att.device)),
-                  'psnd_softmax_keys_bwd')
+        with on(att.device) as hip:
+            hip.psnd_softmax_keys_bwd(att, gatt, B, T, ctx.scale, gs)
         return gs, None, None
 
 
@@ -817,9 +792,8 @@ class Linear1x1(torch.autograd.Function):
         if out_h and pad_h and T % 64:
             ld = (T + 63) // 64 * 64
         y = torch.empty((N, Cout, ld if (out_h and ld) else T), dtype=torch.bfloat16 if out_h else torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_linear1x1_fwd_ex(ptr(x), ptr(w2), ptr(b), N, Cin, Cout, T, int(bool(relu)), int(bool(bf16)), 1 if x_h else (2 if out_h else 0),
-                                              ld, ptr(y), stream_ptr(x.device)), 'psnd_linear1x1_fwd')
+        with on(x.device) as hip:
+            hip.psnd_linear1x1_fwd_ex(x, w2, b, N, Cin, Cout, T, int(bool(relu)), int(bool(bf16)), 1 if x_h else (2 if out_h else 0), ld, y)
         ctx.relu, ctx.has_bias, ctx.wshape, ctx.bf16 = bool(relu), bias is not None, tuple(w.shape), bool(bf16)
         ctx.x_h, ctx.out_h, ctx.t_len = x_h, bool(out_h), T
         ctx.params = (w, bias)
@@ -873,18 +847,15 @@ class Linear1x1(torch.autograd.Function):
             side = cl.param_stream(dev)
             if cl.GRAD_SINK is not None:       # a reducer's bucket waits for the stream that WRITES these gradients (round 5)
                 cl.GRAD_SINK.note_producer(ctx.params, side)
-        with torch.cuda.device(dev):
+        with on(dev) as hip:
             if side is None:
-                check(lib().psnd_linear1x1_bwd_ex(ptr(gy), ptr(y), ptr(x), ptr(w2), N, Cin, Cout, T, int(ctx.bf16), io_h, ld, ptr(addend), ptr(xmask), ptr(gx),
-                                                  ptr(gw), ptr(part), ptr(gb), stream_ptr(dev)), 'psnd_linear1x1_bwd')
+                hip.psnd_linear1x1_bwd_ex(gy, y, x, w2, N, Cin, Cout, T, int(ctx.bf16), io_h, ld, addend, xmask, gx, gw, part, gb)
             else:
                 main = torch.cuda.current_stream(dev)
                 side.wait_stream(main)                          # gy is complete on the main stream
-                check(lib().psnd_linear1x1_bwd_ex(ptr(gy), ptr(y), ptr(x), ptr(w2), N, Cin, Cout, T, int(ctx.bf16), io_h, ld, ptr(addend), ptr(xmask), ptr(gx),
-                                                  None, None, None, stream_ptr(dev)), 'psnd_linear1x1_bwd')
-                with torch.cuda.stream(side):
-                    check(lib().psnd_linear1x1_bwd_ex(ptr(gy), ptr(y), ptr(x), ptr(w2), N, Cin, Cout, T, int(ctx.bf16), io_h, ld, None, None, None, ptr(gw),
-                                                      ptr(part), ptr(gb), stream_ptr(dev)), 'psnd_linear1x1_bwd')
+                hip.psnd_linear1x1_bwd_ex(gy, y, x, w2, N, Cin, Cout, T, int(ctx.bf16), io_h, ld, addend, xmask, gx, None, None, None)
+                with torch.cuda.stream(side), on(dev) as hip_side:
+                    hip_side.psnd_linear1x1_bwd_ex(gy, y, x, w2, N, Cin, Cout, T, int(ctx.bf16), io_h, ld, None, None, None, gw, part, gb)
                 for t in (gy, y, x, w2, gw, part, gb):          # main-stream blocks the side stream reads / writes
                     if t is not None:
                         t.record_stream(side)
@@ -905,8 +876,8 @@ class Im2Col(torch.autograd.Function):
         x = x.contiguous()
         N, C, T = x.shape
         col = torch.empty((N, C * k, To), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_im2col_f32(ptr(x), N, C, T, k, dil, pad, stride, up, To, float(slope), ptr(col), stream_ptr(x.device)), 'psnd_im2col_f32')
+        with on(x.device) as hip:
+            hip.psnd_im2col_f32(x, N, C, T, k, dil, pad, stride, up, To, float(slope), col)
         ctx.geom = (int(k), int(dil), int(pad), int(stride), int(up), int(To), float(slope))
         ctx.save_for_backward(x if slope != 1.0 else None)
         ctx.xshape = (N, C, T)
@@ -919,8 +890,8 @@ class Im2Col(torch.autograd.Function):
         N, C, T = ctx.xshape
         gcol = gcol.contiguous()
         gx = torch.empty((N, C, T), dtype=torch.float32, device=gcol.device)
-        with torch.cuda.device(gcol.device):
-            check(lib().psnd_col2im_f32(ptr(gcol), ptr(x), N, C, T, k, dil, pad, stride, up, To, slope, ptr(gx), stream_ptr(gcol.device)), 'psnd_col2im_f32')
+        with on(gcol.device) as hip:
+            hip.psnd_col2im_f32(gcol, x, N, C, T, k, dil, pad, stride, up, To, slope, gx)
         return gx, None, None, None, None, None, None, None
 
 
@@ -965,8 +936,8 @@ class PosEnc(torch.autograd.Function):
         if pe2.shape[0] != C or pe2.shape[1] < T or not pe2.is_contiguous() or pe2.dtype != torch.float32 or pe2.device != x.device:
             raise PsndError('PosEnc: table %s does not cover a (%d, %d, %d) input' % (tuple(pe.shape), N, C, T))
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_posenc(ptr(x), ptr(pe2), float(scale), N, C, T, pe2.shape[1], ptr(y), stream_ptr(x.device)), 'psnd_posenc')
+        with on(x.device) as hip:
+            hip.psnd_posenc(x, pe2, float(scale), N, C, T, pe2.shape[1], y)
         ctx.scale = float(scale)
         return y
 
@@ -975,8 +946,8 @@ class PosEnc(torch.autograd.Function):
         g = g.contiguous()
         N, C, T = g.shape
         gx = torch.empty_like(g)
-        with torch.cuda.device(g.device):
-            check(lib().psnd_posenc(ptr(g), None, ctx.scale, N, C, T, T, ptr(gx), stream_ptr(g.device)), 'psnd_posenc')
+        with on(g.device) as hip:
+            hip.psnd_posenc(g, None, ctx.scale, N, C, T, T, gx)
         return gx, None, None
 
 
@@ -1009,9 +980,8 @@ class AttentionKVQ(torch.autograd.Function):
         att = torch.empty((heads * N, T, T), dtype=torch.float32, device=dev) if want_att else None
         stats = torch.empty((heads * N, T, 2), dtype=torch.float32, device=dev)
         m = None if mask_u8 is None else mask_u8.contiguous()
-        with torch.cuda.device(dev):
-            check(lib().psnd_mha_fwd(ptr(kvq), ptr(m), N, heads, C, T, ptr(out), ptr(att), ptr(stats), 2 if kvq_h else int(bool(bf16)),
-                                     stream_ptr(dev)), 'psnd_mha_fwd')
+        with on(dev) as hip:
+            hip.psnd_mha_fwd(kvq, m, N, heads, C, T, out, att, stats, 2 if kvq_h else int(bool(bf16)))
         ctx.heads, ctx.bf16 = heads, (2 if kvq_h else int(bool(bf16)))
         ctx.set_materialize_grads(False)             # an unused `att` must not turn into an (H*N, T, T) tensor of zeros in backward
         ctx.save_for_backward(kvq, m, out, att, stats)
@@ -1038,20 +1008,20 @@ class AttentionKVQ(torch.autograd.Function):
         delta = torch.empty((H * N, T), dtype=torch.float32, device=dev)
         gkvq = torch.empty_like(kvq)
         from . import cl
-        args = (ptr(kvq), ptr(m), ptr(out), ptr(att), ptr(stats), ptr(gout), ptr(gatt), N, H, C, T, ptr(delta), ptr(gkvq), ctx.bf16)
-        with torch.cuda.device(dev):
+        args = (kvq, m, out, att, stats, gout, gatt, N, H, C, T, delta, gkvq, ctx.bf16)
+        with on(dev) as hip:
             if ATTN_BWD_TWO_STREAMS and cl.AUTO_SECTIONS and ctx.bf16 != 2:      # (bf16 = 2 runs as a whole: its query kernel forms delta)
                 # the key / value and the query gradient kernels need `delta` only and write disjoint rows of gkvq: two streams (inside
                 # the step graph: two branches) behind the delta launch, joined before the projection's backward reads gkvq
                 main, side = torch.cuda.current_stream(dev), cl.branch_streams(dev, 1)[0]
-                check(lib().psnd_mha_bwd_parts(*args, 1, stream_ptr(dev)), 'psnd_mha_bwd')
+                hip.psnd_mha_bwd_parts(*args, 1)
                 side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    check(lib().psnd_mha_bwd_parts(*args, 4, stream_ptr(dev)), 'psnd_mha_bwd')
-                check(lib().psnd_mha_bwd_parts(*args, 2, stream_ptr(dev)), 'psnd_mha_bwd')
+                with torch.cuda.stream(side), on(dev) as hip_side:
+                    hip_side.psnd_mha_bwd_parts(*args, 4)
+                hip.psnd_mha_bwd_parts(*args, 2)
                 main.wait_stream(side)
             else:
-                check(lib().psnd_mha_bwd(*args, stream_ptr(dev)), 'psnd_mha_bwd')
+                hip.psnd_mha_bwd(*args)
         return gkvq, None, None, None, None
 
 
@@ -1065,8 +1035,8 @@ class PreEmphasisFn(torch.autograd.Function):
         T = x.shape[-1]
         N = x.numel() // max(T, 1)
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_preemphasis_fwd(ptr(x), N, T, float(coef), ptr(y), stream_ptr(x.device)), 'psnd_preemphasis_fwd')
+        with on(x.device) as hip:
+            hip.psnd_preemphasis_fwd(x, N, T, float(coef), y)
         ctx.coef = float(coef)
         return y
 
@@ -1076,8 +1046,8 @@ class PreEmphasisFn(torch.autograd.Function):
         T = gy.shape[-1]
         N = gy.numel() // max(T, 1)
         gx = torch.empty_like(gy)
-        with torch.cuda.device(gy.device):
-            check(lib().psnd_preemphasis_bwd(ptr(gy), N, T, ctx.coef, ptr(gx), stream_ptr(gy.device)), 'psnd_preemphasis_bwd')
+        with on(gy.device) as hip:
+            hip.psnd_preemphasis_bwd(gy, N, T, ctx.coef, gx)
         return gx, None
 
 
@@ -1101,8 +1071,8 @@ class InversePreEmphasisFn(torch.autograd.Function):
         T = x.shape[-1]
         N = x.numel() // max(T, 1)
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_ipreemph_fwd(ptr(x), N, T, ptr(w_ih), ptr(w_hh), int(warm), ptr(y), stream_ptr(x.device)), 'psnd_ipreemph_fwd')
+        with on(x.device) as hip:
+            hip.psnd_ipreemph_fwd(x, N, T, w_ih, w_hh, int(warm), y)
         ctx.save_for_backward(x, y, w_ih, w_hh)
         ctx.warm = int(warm)
         return y
@@ -1116,9 +1086,8 @@ class InversePreEmphasisFn(torch.autograd.Function):
         gx = torch.empty_like(x)
         partial = torch.empty(2 * 256 * max(N, 1) * max((T + IPREEMPH_SPAN - 1) // IPREEMPH_SPAN, 1), dtype=torch.float64, device=x.device)
         gw = torch.empty(2, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_ipreemph_bwd(ptr(gy), ptr(y), ptr(x), N, T, ptr(w_ih), ptr(w_hh), ctx.warm, ptr(gx), ptr(partial), ptr(gw),
-                                          stream_ptr(x.device)), 'psnd_ipreemph_bwd')
+        with on(x.device) as hip:
+            hip.psnd_ipreemph_bwd(gy, y, x, N, T, w_ih, w_hh, ctx.warm, gx, partial, gw)
         need = ctx.needs_input_grad
         return (gx if need[0] else None, gw[0].reshape(w_ih.shape) if need[1] else None, gw[1].reshape(w_hh.shape) if need[2] else None, None)
 
@@ -1176,8 +1145,8 @@ def _lfilter_rows(x, sec, reverse, instance):
     carry = None
     if instance == LFILTER_PARALLEL:
         carry = torch.empty(2 * N * int(lib().psnd_lfilter_spans(T)), dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().psnd_lfilter(ptr(xf), N, T, *sec, int(bool(reverse)), int(instance), ptr(carry), ptr(y), stream_ptr(x.device)), 'psnd_lfilter')
+    with on(x.device) as hip:
+        hip.psnd_lfilter(xf, N, T, *sec, int(bool(reverse)), int(instance), carry, y)
     return y.to(x.dtype)
 
 
@@ -1320,9 +1289,8 @@ def _resample_rows(x, up, down, plan, flip, out_len, device_taps):
     xf = x.detach().contiguous().float()
     N = math.prod(xf.shape[:-1])                         # rows, also where T == 0: those write zeros
     y = torch.empty(xf.shape[:-1] + (out_len,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().psnd_resample(ptr(xf), N, T, ptr(h), taps, up, down, int(bool(flip)), ptr(y), out_len, stream_ptr(x.device)),
-              'psnd_resample')
+    with on(x.device) as hip:
+        hip.psnd_resample(xf, N, T, h, taps, up, down, int(bool(flip)), y, out_len)
     return y.to(x.dtype)
 
 
@@ -1505,9 +1473,8 @@ def silence_ranges(wav, min_silence_len, silence_thresh, seek_step=1, lengths=No
     ranges = torch.empty((N, cap, 2), dtype=torch.int64, device=wav.device)
     nbytes = int(lib().psnd_silence_scratch_bytes(N, T, L, s))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=wav.device) if nbytes else None
-    with torch.cuda.device(wav.device):
-        check(lib().psnd_silence_ranges(ptr(xf), N, T, ptr(lengths), L, s, theta, ptr(scratch), ptr(count), ptr(ranges), cap,
-                                        stream_ptr(wav.device)), 'psnd_silence_ranges')
+    with on(wav.device) as hip:
+        hip.psnd_silence_ranges(xf, N, T, lengths, L, s, theta, scratch, count, ranges, cap)
     return count, ranges
 
 
@@ -1519,9 +1486,8 @@ def volnorm_forward(wav, window, hop, inv_gain, out_len):
     hops = (L - window + hop - 1) // hop
     out = torch.empty((B, out_len), dtype=torch.float32, device=wav.device)
     std = torch.empty(hops, dtype=torch.float32, device=wav.device)
-    with torch.cuda.device(wav.device):
-        check(lib().psnd_volnorm_fwd(ptr(wav), B, L, int(window), int(hop), float(inv_gain), ptr(out), int(out_len), ptr(std),
-                                     stream_ptr(wav.device)), 'psnd_volnorm_fwd')
+    with on(wav.device) as hip:
+        hip.psnd_volnorm_fwd(wav, B, L, int(window), int(hop), float(inv_gain), out, int(out_len), std)
     return out, std
 
 
@@ -1534,9 +1500,8 @@ def volnorm_reverse(wav, window, hop, gain, std, out_len):
     if std.numel() < (L - window + hop - 1) // hop:
         raise _lib.PsndError('volnorm_reverse: %d deviations for %d hops' % (std.numel(), (L - window + hop - 1) // hop))
     out = torch.empty((B, out_len), dtype=torch.float32, device=wav.device)
-    with torch.cuda.device(wav.device):
-        check(lib().psnd_volnorm_reverse(ptr(wav), B, L, int(window), int(hop), float(gain), ptr(std), ptr(out), int(out_len),
-                                         stream_ptr(wav.device)), 'psnd_volnorm_reverse')
+    with on(wav.device) as hip:
+        hip.psnd_volnorm_reverse(wav, B, L, int(window), int(hop), float(gain), std, out, int(out_len))
     return out
 
 
@@ -1589,8 +1554,7 @@ class MultiStftLossFn(torch.autograd.Function):
         # training case (only the prediction needs a gradient): the prediction's magnitudes never reach HBM - psnd_stft_fwd_msl leaves
         # the three sums, psnd_stft_bwd_msl recomputes |X| in the backward
         only_pred = not ctx.needs_input_grad[1]
-        with torch.cuda.device(dev):
-            s = stream_ptr(dev)
+        with on(dev) as hip:
             for (n_fft, hop), plan in zip(cfgs, plans):
                 t = stft_forward(target, n_fft, hop, plan)['mag']
                 KF = t.shape[1] * t.shape[2]
@@ -1598,23 +1562,22 @@ class MultiStftLossFn(torch.autograd.Function):
                 if B > 0:
                     p = None
                     part = torch.empty((N, B, 3), dtype=torch.float64, device=dev)
-                    check(lib().psnd_stft_fwd_msl(ptr(pred), N, pred.shape[1], int(n_fft), int(hop), ptr(plan), 0.0, ptr(t), float(eps),
-                                                  ptr(part), s), 'psnd_stft_fwd_msl')
+                    hip.psnd_stft_fwd_msl(pred, N, pred.shape[1], int(n_fft), int(hop), plan, 0.0, t, float(eps), part)
                 else:
                     p = stft_forward(pred, n_fft, hop, plan)['mag']
                     B = int(lib().psnd_stft_loss_blocks(KF))
                     part = torch.empty((N, B, 3), dtype=torch.float64, device=dev)
-                    check(lib().psnd_stft_loss_partial(ptr(p), ptr(t), N, KF, float(eps), ptr(part), s), 'psnd_stft_loss_partial')
+                    hip.psnd_stft_loss_partial(p, t, N, KF, float(eps), part)
                 mags.append((p, t))
                 parts.append(part)
                 kfs.append(KF)
                 blocks.append(B)
             norms = torch.empty((L, N, 2), dtype=torch.float32, device=dev)
             out = torch.empty(3, dtype=torch.float32, device=dev)
-            parr = (ctypes.c_void_p * L)(*[ptr(q) for q in parts])
+            parr = (ctypes.c_void_p * L)(*[q.data_ptr() for q in parts])
             karr = (ctypes.c_int64 * L)(*kfs)
             barr = (ctypes.c_int64 * L)(*blocks)
-            check(lib().psnd_stft_loss_final_blocks(parr, karr, barr, L, N, ptr(norms), ptr(out), s), 'psnd_stft_loss_final_blocks')
+            hip.psnd_stft_loss_final_blocks(parr, karr, barr, L, N, norms, out)
         ctx.cfgs, ctx.eps, ctx.kfs = cfgs, float(eps), kfs
         ctx.has_p = [pt[0] is not None for pt in mags]
         ctx.save_for_backward(pred, target, norms, *[m if m is not None else norms for pt in mags for m in pt], *plans)
@@ -1630,8 +1593,7 @@ class MultiStftLossFn(torch.autograd.Function):
         need_p, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g = g.contiguous().float()
         gpred = gtarget = None
-        with torch.cuda.device(pred.device):
-            s = stream_ptr(pred.device)
+        with on(pred.device) as hip:
             for i, (n_fft, hop) in enumerate(ctx.cfgs):
                 p, t = mags[2 * i], mags[2 * i + 1]
                 if not ctx.has_p[i] or (need_p and not need_t and _msl_fused(n_fft, hop)):
@@ -1640,13 +1602,12 @@ class MultiStftLossFn(torch.autograd.Function):
                     acc = gpred is not None
                     if not acc:
                         gpred = torch.empty_like(pred)
-                    check(lib().psnd_stft_bwd_msl(ptr(pred), N, pred.shape[1], n_fft, hop, FRAMING_CENTER, ptr(plans[i]), 0.0, ptr(t),
-                                                  ptr(norms[i]), ptr(g), L, ctx.eps, int(acc), ptr(gpred), s), 'psnd_stft_bwd_msl')
+                    hip.psnd_stft_bwd_msl(pred, N, pred.shape[1], n_fft, hop, FRAMING_CENTER, plans[i], 0.0, t, norms[i], g, L, ctx.eps, int(acc),
+                                          gpred)
                     continue
                 gp = torch.empty_like(p) if need_p else None
                 gt = torch.empty_like(t) if need_t else None
-                check(lib().psnd_stft_loss_bwd(ptr(p), ptr(t), N, ctx.kfs[i], ctx.eps, ptr(norms[i]), ptr(g), L, ptr(gp), ptr(gt), s),
-                      'psnd_stft_loss_bwd')
+                hip.psnd_stft_loss_bwd(p, t, N, ctx.kfs[i], ctx.eps, norms[i], g, L, gp, gt)
                 if need_p:
                     gw = stft_backward(pred, n_fft, hop, plans[i], gmag=gp)
                     gpred = gw if gpred is None else gpred.add_(gw)
@@ -1663,18 +1624,16 @@ def _pqmf(op, x, filt, subbands, taps, flip, scale, t_out=None):
     _need_cuda(x, 'input')
     x, filt = x.contiguous(), filt.contiguous()
     dev = x.device
-    with torch.cuda.device(dev):
+    with on(dev) as hip:
         if op == 'analysis':                        # (B, T) -> (B, S, T // S)
             B, T = x.shape
             out = torch.empty((B, subbands, T // subbands), dtype=torch.float32, device=dev)
-            check(lib().psnd_pqmf_analysis(ptr(x), ptr(filt), B, T, subbands, taps, int(flip), float(scale), ptr(out), stream_ptr(dev)),
-                  'psnd_pqmf_analysis')
+            hip.psnd_pqmf_analysis(x, filt, B, T, subbands, taps, int(flip), float(scale), out)
         else:                                       # (B, S, M) -> (B, M * S)
             B, S, M = x.shape
             t_out = M * S if t_out is None else t_out
             out = torch.empty((B, t_out), dtype=torch.float32, device=dev)
-            check(lib().psnd_pqmf_synthesis(ptr(x), ptr(filt), B, M, t_out, subbands, taps, int(flip), float(scale), ptr(out), stream_ptr(dev)),
-                  'psnd_pqmf_synthesis')
+            hip.psnd_pqmf_synthesis(x, filt, B, M, t_out, subbands, taps, int(flip), float(scale), out)
     return out
 
 
@@ -1719,8 +1678,8 @@ class L1Loss(torch.autograd.Function):
         n = a.numel()
         part = torch.empty(int(lib().psnd_l1_loss_blocks(n)), dtype=torch.float64, device=a.device)
         out = torch.empty((), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            check(lib().psnd_l1_loss_fwd(ptr(a), ptr(b), n, ptr(part), ptr(out), stream_ptr(a.device)), 'psnd_l1_loss_fwd')
+        with on(a.device) as hip:
+            hip.psnd_l1_loss_fwd(a, b, n, part, out)
         ctx.save_for_backward(a, b)
         return out
 
@@ -1730,8 +1689,8 @@ class L1Loss(torch.autograd.Function):
         ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         g = g.contiguous().float()
-        with torch.cuda.device(a.device):
-            check(lib().psnd_l1_loss_bwd(ptr(a), ptr(b), a.numel(), ptr(g), ptr(ga), ptr(gb), stream_ptr(a.device)), 'psnd_l1_loss_bwd')
+        with on(a.device) as hip:
+            hip.psnd_l1_loss_bwd(a, b, a.numel(), g, ga, gb)
         return ga, gb
 
 
@@ -1761,8 +1720,8 @@ class L1LossSum(torch.autograd.Function):
         pb = (ctypes.c_void_p * k)(*[ab[2 * i + 1].data_ptr() for i in range(k)])
         pn = (ctypes.c_int64 * k)(*ns)
         pw = (ctypes.c_double * k)(*[float(w) for w in weights])
-        with torch.cuda.device(dev):
-            check(lib().psnd_l1_loss_sum_fwd(pa, pb, pn, pw, k, ptr(part), ptr(out), stream_ptr(dev)), 'psnd_l1_loss_sum_fwd')
+        with on(dev) as hip:
+            hip.psnd_l1_loss_sum_fwd(pa, pb, pn, pw, k, part, out)
         ctx.weights = tuple(float(w) for w in weights)
         ctx.save_for_backward(*ab)
         return out
@@ -1772,14 +1731,13 @@ class L1LossSum(torch.autograd.Function):
         ab = ctx.saved_tensors
         g = g.contiguous().float()
         grads = []
-        with torch.cuda.device(g.device):
+        with on(g.device) as hip:
             for i, w in enumerate(ctx.weights):
                 a, b = ab[2 * i], ab[2 * i + 1]
                 ga = torch.empty_like(a) if ctx.needs_input_grad[1 + 2 * i] else None
                 gb = torch.empty_like(b) if ctx.needs_input_grad[2 + 2 * i] else None
                 if ga is not None or gb is not None:
-                    check(lib().psnd_l1_loss_bwd_w(ptr(a), ptr(b), a.numel(), ptr(g), w, ptr(ga), ptr(gb), stream_ptr(g.device)),
-                          'psnd_l1_loss_bwd_w')
+                    hip.psnd_l1_loss_bwd_w(a, b, a.numel(), g, w, ga, gb)
                 grads += [ga, gb]
         return (None,) + tuple(grads)
 
@@ -1801,8 +1759,8 @@ class MaskedL1(torch.autograd.Function):
         part = torch.empty(2 * int(lib().psnd_masked_l1_blocks(a.numel())), dtype=torch.float64, device=a.device)
         out = torch.empty((), dtype=torch.float32, device=a.device)
         inv = torch.empty(1, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            check(lib().psnd_masked_l1_fwd(ptr(a), ptr(b), ptr(w), N, C, T, ptr(part), ptr(out), ptr(inv), stream_ptr(a.device)), 'psnd_masked_l1_fwd')
+        with on(a.device) as hip:
+            hip.psnd_masked_l1_fwd(a, b, w, N, C, T, part, out, inv)
         ctx.save_for_backward(a, b, w, inv)
         return out
 
@@ -1815,8 +1773,8 @@ class MaskedL1(torch.autograd.Function):
         gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         if ga is None and gb is None:
             return None, None, None
-        with torch.cuda.device(a.device):
-            check(lib().psnd_masked_l1_bwd(ptr(a), ptr(b), ptr(w), N, C, T, ptr(g), ptr(inv), ptr(ga), ptr(gb), stream_ptr(a.device)), 'psnd_masked_l1_bwd')
+        with on(a.device) as hip:
+            hip.psnd_masked_l1_bwd(a, b, w, N, C, T, g, inv, ga, gb)
         return ga, gb, None
 
 
@@ -1859,9 +1817,8 @@ def lstft_analysis(x, basis, window, hop, polar=False):
     spec = torch.empty((N, C, max(F, 0)), dtype=torch.float32, device=x.device)
     mag = torch.empty((N, C // 2, max(F, 0)), dtype=torch.float32, device=x.device) if polar else None
     phase = torch.empty_like(mag) if polar else None
-    with torch.cuda.device(x.device):
-        check(lib().psnd_lstft_analysis(ptr(x), ptr(b), ptr(w), N, Lx, C, n, int(hop), ptr(spec), ptr(mag), ptr(phase), stream_ptr(x.device)),
-              'psnd_lstft_analysis')
+    with on(x.device) as hip:
+        hip.psnd_lstft_analysis(x, b, w, N, Lx, C, n, int(hop), spec, mag, phase)
     return (spec, mag, phase) if polar else spec
 
 
@@ -1881,9 +1838,8 @@ def lstft_synthesis(g, basis, window, hop, mult=None, length=None):
             raise PsndError('lstft_synthesis: a multiplier of %d samples for rows of %d' % (mult.numel(), L))
         mult = mult.contiguous()
     y = torch.empty((N, L), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        check(lib().psnd_lstft_synthesis(ptr(g), ptr(b), ptr(w), ptr(mult), N, C, F, n, int(hop), L, ptr(y), stream_ptr(g.device)),
-              'psnd_lstft_synthesis')
+    with on(g.device) as hip:
+        hip.psnd_lstft_synthesis(g, b, w, mult, N, C, F, n, int(hop), L, y)
     return y
 
 
@@ -1896,9 +1852,8 @@ def lstft_basis_grad(g, x, window, hop, like):
     slabs = int(lib().psnd_lstft_wgrad_slabs(N, C, n, F))
     part = torch.empty((max(slabs, 1), C, n), dtype=torch.float32, device=g.device)
     gb = torch.empty((C, n), dtype=torch.float32, device=g.device)
-    with torch.cuda.device(g.device):
-        check(lib().psnd_lstft_basis_grad(ptr(g), ptr(x), ptr(w), N, Lx, C, n, int(hop), F, ptr(part), ptr(gb), stream_ptr(g.device)),
-              'psnd_lstft_basis_grad')
+    with on(g.device) as hip:
+        hip.psnd_lstft_basis_grad(g, x, w, N, Lx, C, n, int(hop), F, part, gb)
     return gb.view(like.shape)
 
 
@@ -1925,8 +1880,8 @@ class LstftAnalysis(torch.autograd.Function):
         gmag = gmag.contiguous().float()
         N, C, F = spec.shape
         gspec = torch.empty_like(spec)
-        with torch.cuda.device(x.device):
-            check(lib().psnd_lstft_mag_bwd(ptr(spec), ptr(mag), ptr(gmag), N, C, F, ptr(gspec), stream_ptr(x.device)), 'psnd_lstft_mag_bwd')
+        with on(x.device) as hip:
+            hip.psnd_lstft_mag_bwd(spec, mag, gmag, N, C, F, gspec)
         if ctx.needs_input_grad[0]:
             gx = lstft_synthesis(gspec, basis, window, ctx.hop, None, x.shape[1])
         if ctx.needs_input_grad[1]:

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, check, ptr, stream_ptr
+from ._lib import lib, on
 
 
 class Adam(torch.optim.Optimizer):
@@ -147,14 +147,12 @@ class Adam(torch.optim.Optimizer):
                 scratch = self._plans['clip'] = {'sumsq': torch.zeros((), dtype=torch.float64, device=device),
                                                  'coef': torch.ones(2, dtype=torch.float32, device=device)}
             gs = grad_scale.to(device=device, dtype=torch.float32) if grad_scale is not None else None
-            with torch.cuda.device(device):
+            with on(device) as hip:
                 for wi, (group, plan, n, _) in enumerate(work):
                     if plan.get('partial') is None:
                         plan['partial'] = torch.empty(plan['chunk_off'].numel(), dtype=torch.float64, device=device)
-                    check(lib().psnd_grad_sumsq(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
-                                                plan['chunk_off'].numel(), clip_value, ptr(gs), int(wi > 0), max_norm,
-                                                ptr(plan['partial']), ptr(scratch['sumsq']), ptr(scratch['coef']), stream_ptr(device)),
-                          'psnd_grad_sumsq')
+                    hip.psnd_grad_sumsq(plan['table'], n, plan['chunk_tensor'], plan['chunk_off'], plan['chunk_off'].numel(), clip_value, gs,
+                                        int(wi > 0), max_norm, plan['partial'], scratch['sumsq'], scratch['coef'])
             coef = scratch['coef']
             self.last_grad_norm = coef[1]
         flag_log = getattr(self, 'flag_log', None)
@@ -172,24 +170,22 @@ class Adam(torch.optim.Optimizer):
         for wi, (group, plan, n, gi) in enumerate(work):
             device = plan['device']
             b1, b2 = group['betas']
-            log_ptr, log_slot, log_seq = (ptr(flag_log[0]), int(flag_log[1]), int(flag_log[2])) if (flag_log is not None and wi == 0) else (None, 0, 0)
+            log_ptr, log_slot, log_seq = (flag_log[0], int(flag_log[1]), int(flag_log[2])) if (flag_log is not None and wi == 0) else (None, 0, 0)
             fi = found_inf.to(device=device, dtype=torch.float32) if found_inf is not None else None
             gs = grad_scale.to(device=device, dtype=torch.float32) if grad_scale is not None else None
             if lr_ahead is not None:
                 if good_count.device != device:
                     raise _lib.PsndError('lr_ahead: counter on %s, parameters on %s' % (good_count.device, device))
-                with torch.cuda.device(device):
-                    check(lib().psnd_adam_step_sched(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
-                                                     plan['chunk_off'].numel(), float(b1), float(b2), float(group['eps']),
-                                                     float(group['weight_decay']), int(self._decoupled), ptr(fi), ptr(gs), ptr(plan['corr']),
-                                                     clip_value, ptr(coef), log_ptr, log_slot, log_seq, ptr(lr_ring), int(lr_rows), n_groups, gi,
-                                                     ptr(good_count), int(wi == len(work) - 1), stream_ptr(device)), 'psnd_adam_step_sched')
+                with on(device) as hip:
+                    hip.psnd_adam_step_sched(plan['table'], n, plan['chunk_tensor'], plan['chunk_off'], plan['chunk_off'].numel(), float(b1),
+                                             float(b2), float(group['eps']), float(group['weight_decay']), int(self._decoupled), fi, gs, plan['corr'],
+                                             clip_value, coef, log_ptr, log_slot, log_seq, lr_ring, int(lr_rows), n_groups, gi, good_count,
+                                             int(wi == len(work) - 1))
                 continue
-            with torch.cuda.device(device):
-                check(lib().psnd_adam_step_logged(ptr(plan['table']), n, ptr(plan['chunk_tensor']), ptr(plan['chunk_off']),
-                                                  plan['chunk_off'].numel(), float(group['lr']), float(b1), float(b2), float(group['eps']),
-                                                  float(group['weight_decay']), int(self._decoupled), ptr(fi), ptr(gs), ptr(plan['corr']),
-                                                  clip_value, ptr(coef), log_ptr, log_slot, log_seq, stream_ptr(device)), 'psnd_adam_step')
+            with on(device) as hip:
+                hip.psnd_adam_step_logged(plan['table'], n, plan['chunk_tensor'], plan['chunk_off'], plan['chunk_off'].numel(), float(group['lr']),
+                                          float(b1), float(b2), float(group['eps']), float(group['weight_decay']), int(self._decoupled), fi, gs,
+                                          plan['corr'], clip_value, coef, log_ptr, log_slot, log_seq)
         return loss
 
 

@@ -721,10 +721,10 @@ class Trainer:
             return ready
         x = loss.detach()
         if x.is_cuda and x.dtype == torch.float32 and x.is_contiguous():
-            from ._lib import lib, ptr, stream_ptr, check
+            from ._lib import on
             flag = torch.empty((), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                check(lib().psnd_nan_flag(ptr(x), x.numel(), ptr(flag), stream_ptr(x.device)), 'psnd_nan_flag')
+            with on(x.device) as hip:
+                hip.psnd_nan_flag(x, x.numel(), flag)
             return flag
         return torch.isnan(x).any().to(torch.float32).reshape(())
 

@@ -144,6 +144,31 @@ def test_a_missing_header_is_an_error_that_names_the_path(monkeypatch):
         _lib._read_header()
 
 
+# ---- the launcher (_lib.on) serves the entry points that take a stream, and only those -------------------------------------------------------
+def test_launchable_entry_points_are_those_whose_last_parameter_is_the_stream(L):
+    """against a regex of this file's own over the header text (the lab block included)"""
+    txt = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'psnd.h')).read(), flags=re.S)
+    want = set(re.findall(r'\b(psnd_\w+)\s*\([^()]*\bvoid\s*\*\s*stream\s*\)\s*;', txt))
+    assert len(want) >= 100 and want == set(L.LAUNCHABLE)
+    for name in ('psnd_frame_count', 'psnd_stft_plan_bytes', 'psnd_last_error', 'psnd_stream_wait_event'):
+        assert name in L.SIGNATURES and name not in L.LAUNCHABLE
+    assert all(L.SIGNATURES[n][0] is ctypes.c_int and L.SIGNATURES[n][1][-1] is ctypes.c_void_p for n in L.LAUNCHABLE & set(L.SIGNATURES))
+    assert 'psnd_a' not in L.LAUNCHABLE                          # parsing other header text leaves the module's set alone
+    streamed = set()
+    L.parse_header(GOOD + 'int psnd_b(void *stream, int x);\nvoid psnd_c(void *stream);\n', streamed)
+    assert streamed == {'psnd_a'}
+
+
+def test_launcher_resolves_names_without_entering(L):
+    k = L.on(0)                                                  # not entered: no device is touched
+    with pytest.raises(AttributeError, match='psnd_no_such_entry'):
+        k.psnd_no_such_entry
+    with pytest.raises(L.PsndError, match='psnd_stft_plan_bytes'):
+        k.psnd_stft_plan_bytes
+    assert not hasattr(k, 'psnd_no_such_entry')
+    assert callable(k.psnd_stft_fwd)
+
+
 def test_frame_contract_matches_oracle(L):
     lib = L.lib()
     for T, n, h in [(44100, 1024, 256), (8192, 1024, 256), (1323000, 4096, 1024), (700, 256, 64), (2049, 1024, 255),

@@ -329,6 +329,6 @@ def test_missing_library_raises(monkeypatch):
 
     def gone():
         raise _lib.PsndError('libpsnd_hip.so not found')
-    monkeypatch.setattr('pytorch_sound_amd.kernels.lib', gone)
+    monkeypatch.setattr('pytorch_sound_amd._lib.lib', gone)         # the one loader every launch goes through (_lib.on)
     with pytest.raises(_lib.PsndError):
         m.transform(torch.zeros(1, 1000, device=dev))
