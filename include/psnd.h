@@ -725,6 +725,42 @@ size_t psnd_silence_scratch_bytes(int64_t N, int64_t T, int64_t L, int64_t s);
 int psnd_silence_ranges(const float *x, int64_t N, int64_t T, const int64_t *lengths, int64_t L, int64_t s, double theta, void *scratch,
                         int32_t *count, int64_t *ranges, int64_t cap, void *stream);
 
+/* ---- fundamental frequency per frame on device tensors (psnd_pitch.hip): the place of utils/sound.py get_f0 (:38-49), which calls WORLD's
+ *  DIO + StoneMask through pyworld.  What is computed here is NOT WORLD: it is YIN (de Cheveigne & Kawahara, JASA 111 (4), 2002), steps
+ *  1-5, as written out below; parity with WORLD is unpinned.  Kept of the reference's contract: one value per frame at the times
+ *  i hop / sr, T / hop + 1 frames (WORLD's GetSamplesForDIO for frame_period = 1000 hop / sr in exact integers), 0 for an unvoiced frame.
+ *  Every row x of T_r samples (fp32) on its own.  Caller's parameters: hop >= 1, W >= tau_max >= tau_min >= 2, threshold > 0, sr > 0
+ *  (utils.pitch derives tau_min = max(2, floor(sr / f0_ceil)), tau_max = ceil(sr / f0_floor), W = 2 tau_max).  span = W + tau_max,
+ *  H = span / 2 (integer division).
+ *    Frames.   F_r = T_r / hop + 1.  Frame i reads u[j] = x[i hop - H + j], j < span; samples outside [0, T_r) are zeros.
+ *    1  d(tau) = sum_{j < W} (u[j] - u[j + tau])^2, tau = 1 .. tau_max: the direct sum of squared differences in fp32, j ascending - not
+ *       energy minus autocorrelation (it cancels), no running sum from frame to frame.
+ *    2  d'(tau) = d(tau) tau / sum_{k = 1 .. tau} d(k); 1 where that sum is 0.
+ *    3  t0 = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold.  None: the frame is unvoiced, lag = 0, f0 = 0,
+ *       aperiodicity = min d' over that range.
+ *    4  t = t0; while t + 1 <= tau_max and d'(t + 1) < d'(t): t = t + 1.
+ *    5  if t - 1 >= 1 and t + 1 <= tau_max: y0, y1, y2 = d'(t - 1), d'(t), d'(t + 1), den = y0 - 2 y1 + y2,
+ *       off = clamp((y0 - y2) / (2 den), -1/2, 1/2) if den > 0, else 0; otherwise off = 0.  f0 = sr / (t + off), lag = t,
+ *       aperiodicity = d'(t).
+ *    6  A frame whose span holds a NaN or an Inf is unvoiced with aperiodicity 1, decided by a test of the exponent bits before step 1.
+ *    Outputs.  f0, aperiodicity (fp32), lag (int32), each (N, F) with F >= psnd_yin_frames(T, hop); EVERY slot is written: the slots of
+ *              row r from F_r on hold f0 = 0, aperiodicity = 1, lag = 0.
+ *  lengths : per-row valid lengths (device int64, clamped to [0, T]) or NULL for T everywhere; samples at or behind a row's length are
+ *      read as zeros whatever the memory holds (no global read leaves [0, T_r)).  x may start on any 4-byte boundary.
+ *  One launch, no scratch, no atomics: a workgroup of 4 waves takes 4 consecutive frames of a row, stages their spans in LDS once (the
+ *  union when hop < span, back to back otherwise), one wave per frame, lane l the lags 1 + l + 64 k; the prefix sum of step 2 is a wave
+ *  scan in fp32, step 3 a ballot, steps 4-5 a walk over d' in LDS.
+ *  Limits: span = W + tau_max <= psnd_yin_max_span() = 6144 (4 spans and 4 rows of d' share the LDS; 48 kHz with a 50 Hz floor is
+ *      tau_max = 960, W = 1920, span = 2880; 44.1 kHz down to 22 Hz with W = 2 tau_max fits as well); at most 2^31 - 1 workgroups.
+ *  PSND_E_ARG before anything is launched: hop < 1, tau_min < 2, tau_max < tau_min, W < tau_max, span beyond the limit, a NaN or
+ *      non-positive threshold or sr, F < psnd_yin_frames(T, hop), N or T < 0, a NULL pointer with N > 0 (x may be NULL when T == 0);
+ *      more workgroups than the grid holds: PSND_E_SHAPE.  N == 0: PSND_OK, nothing launched.
+ *  psnd_yin_frames(T, hop): T / hop + 1 (0 for T < 0 or hop < 1; host helper). */
+int64_t psnd_yin_frames(int64_t T, int64_t hop);
+int64_t psnd_yin_max_span(void);
+int psnd_yin_f0(const float *x, int64_t N, int64_t T, const int64_t *lengths, int64_t hop, int64_t W, int64_t tau_min, int64_t tau_max,
+                float threshold, double sr, float *f0, float *aperiodicity, int32_t *lag, int64_t F, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

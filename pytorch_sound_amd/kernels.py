@@ -2,7 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly` and `silence_ranges` alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges` and `yin_f0` alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
@@ -1476,6 +1476,135 @@ def silence_ranges(wav, min_silence_len, silence_thresh, seek_step=1, lengths=No
     with on(wav.device) as hip:
         hip.psnd_silence_ranges(xf, N, T, lengths, L, s, theta, scratch, count, ranges, cap)
     return count, ranges
+
+
+def _count(name, v, least):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+        raise ValueError('yin: %s=%r - a count of samples, at least %d' % (name, v, least))
+    return int(v)
+
+
+def yin_lags(sr, f0_floor=71.0, f0_ceil=800.0, frame_length=None):
+    """(tau_min, tau_max, W) of include/psnd.h from a search range in Hz: tau_min = max(2, floor(sr / f0_ceil)), tau_max = ceil(sr / f0_floor),
+    W = frame_length or 2 tau_max.  ValueError on a rate or a range that is not positive and finite, an empty range, or W < tau_max."""
+    sr, lo, hi = float(sr), float(f0_floor), float(f0_ceil)
+    for name, v in (('sr', sr), ('f0_floor', lo), ('f0_ceil', hi)):
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError('yin: %s=%r - positive and finite' % (name, v))
+    if sr / lo > 2.0 ** 31:
+        raise ValueError('yin: f0_floor=%r at sr=%r is a lag of more than 2^31 samples' % (lo, sr))
+    tau_min, tau_max = max(2, math.floor(sr / hi)), math.ceil(sr / lo)
+    if tau_max < tau_min:
+        raise ValueError('yin: no lag between f0_ceil=%r and f0_floor=%r at sr=%r (tau_min=%d, tau_max=%d)' % (hi, lo, sr, tau_min, tau_max))
+    W = 2 * tau_max if frame_length is None else _count('frame_length', frame_length, 1)
+    if W < tau_max:
+        raise ValueError('yin: frame_length=%d is shorter than the longest lag tau_max=%d' % (W, tau_max))
+    return tau_min, tau_max, W
+
+
+def yin_frames(T, hop):
+    """psnd_yin_frames: T // hop + 1 frames, at the samples 0, hop, 2 hop, ..."""
+    return int(T) // _count('hop', hop, 1) + 1
+
+
+def yin_threshold(threshold):
+    th = float(threshold)
+    if not th > 0.0:
+        raise ValueError('yin: threshold=%r - positive' % (threshold,))
+    return th
+
+
+def yin_f0_host(x, hop, sr, tau_min, tau_max, W, threshold, chunk=256):
+    """the definition of include/psnd.h (YIN steps 1-5 and the non-finite rule) on one row of numpy samples in float64, vectorised over the
+    frames and over j, `chunk` frames at a time: (f0, aperiodicity, lag) as float64, float64, int32 arrays of yin_frames(T, hop) entries"""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    T, F = x.shape[0], x.shape[0] // hop + 1
+    span = W + tau_max
+    H = span // 2
+    xp = np.concatenate((np.zeros(H), x, np.zeros(span)))              # frame i reads xp[i hop : i hop + span]: i hop <= T
+    f0, ap, lag = np.zeros(F), np.ones(F), np.zeros(F, dtype=np.int32)
+    taus = np.arange(1, tau_max + 1)
+    rng = (taus >= tau_min)
+    for a in range(0, F, chunk):
+        idx = np.arange(a, min(a + chunk, F))
+        U = xp[idx[:, None] * hop + np.arange(span)]
+        bad = ~np.isfinite(U).all(axis=1)
+        U[bad] = 0.0
+        d = np.empty((idx.size, tau_max))
+        for tau in taus:
+            e = U[:, :W] - U[:, tau:tau + W]
+            d[:, tau - 1] = (e * e).sum(axis=1)
+        cs = np.cumsum(d, axis=1)
+        dp = np.where(cs == 0.0, 1.0, d * taus / np.where(cs == 0.0, 1.0, cs))
+        under = (dp < threshold) & rng
+        voiced = under.any(axis=1) & ~bad
+        t0 = under.argmax(axis=1)                                       # index of the lag t0 = index + 1
+        last = np.ones((idx.size, 1), dtype=bool)
+        stop = np.concatenate((~(dp[:, 1:] < dp[:, :-1]), last), axis=1) & (np.arange(tau_max) >= t0[:, None])
+        k = stop.argmax(axis=1)                                         # the descent ends at the lag k + 1
+        rows = np.arange(idx.size)
+        y1 = dp[rows, k]
+        inner = (k >= 1) & (k + 1 <= tau_max - 1)
+        y0, y2 = dp[rows, np.maximum(k - 1, 0)], dp[rows, np.minimum(k + 1, tau_max - 1)]
+        den = y0 - 2.0 * y1 + y2
+        ok = inner & (den > 0.0)
+        off = np.where(ok, np.clip(0.5 * (y0 - y2) / np.where(ok, den, 1.0), -0.5, 0.5), 0.0)
+        f0[idx] = np.where(voiced, sr / (k + 1 + off), 0.0)
+        lag[idx] = np.where(voiced, k + 1, 0)
+        ap[idx] = np.where(bad, 1.0, np.where(voiced, y1, np.where(rng, dp, np.inf).min(axis=1)))
+    return f0, ap, lag
+
+
+def yin_f0(wav, hop, sr=22050, f0_floor=71.0, f0_ceil=800.0, threshold=0.1, frame_length=None, lengths=None):
+    """fundamental frequency per frame of every row of `wav` (..., T) by the definition of include/psnd.h (YIN, steps 1-5):
+    (f0 float32, aperiodicity float32, lag int32), each (..., F) on wav's device, F = T // hop + 1, frame i at the sample i hop.  An
+    unvoiced frame has f0 = 0 and lag = 0.  `lengths`: per-row valid lengths, clamped to [0, T]; row n then has lengths[n] // hop + 1 frames,
+    its samples from lengths[n] on count as zeros and its remaining slots hold (0, 1, 0).
+
+    HIP tensors run psnd_yin_f0 (float32; float16 / bfloat16 are cast; float64 raises) in one launch with no host synchronisation - the
+    call can be captured; `lengths` is then an int64 tensor on the same device (anything else is copied there).  CPU tensors go through
+    yin_f0_host in float64.  No autograd: a lag is an integer and f0 jumps with it."""
+    if not isinstance(wav, torch.Tensor):
+        raise _lib.PsndError('yin: a tensor is expected, got %s' % type(wav).__name__)
+    if wav.dim() == 0:
+        raise _lib.PsndError('yin: the input needs a time axis')
+    if not wav.is_floating_point():
+        raise _lib.PsndError('yin: floating input expected, got %s' % wav.dtype)
+    hop = _count('hop', hop, 1)
+    tau_min, tau_max, W = yin_lags(sr, f0_floor, f0_ceil, frame_length)
+    th = yin_threshold(threshold)
+    lead, T = tuple(wav.shape[:-1]), wav.shape[-1]
+    N = math.prod(lead)
+    F = yin_frames(T, hop)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths)
+        if lengths.is_floating_point() or lengths.numel() != N:
+            raise _lib.PsndError('yin: lengths must be %d integers, got %s %s' % (N, tuple(lengths.shape), lengths.dtype))
+    if not wav.is_cuda:
+        rows = wav.detach().reshape(N, T).to(torch.float64).numpy()
+        lens = [T] * N if lengths is None else [min(max(int(v), 0), T) for v in lengths.reshape(-1).tolist()]
+        f0, ap, lag = np.zeros((N, F), np.float32), np.ones((N, F), np.float32), np.zeros((N, F), np.int32)
+        for n in range(N):
+            r = yin_f0_host(rows[n, :lens[n]], hop, float(sr), tau_min, tau_max, W, th)
+            f0[n, :r[0].size], ap[n, :r[0].size], lag[n, :r[0].size] = r
+        return tuple(torch.from_numpy(a).reshape(lead + (F,)) for a in (f0, ap, lag))
+    if wav.dtype == torch.float64:
+        raise _lib.PsndError('yin: no float64 instance on HIP tensors (a round trip through float32 would silently change which lag passes '
+                             'the threshold): pass a float32 tensor, or a CPU tensor in float64')
+    if wav.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.PsndError('yin: floating input expected, got %s' % wav.dtype)
+    xf = wav.detach().reshape(N, T).float()
+    if N * T > 0 and (xf.stride(-1) != 1 or (N > 1 and xf.stride(0) != T)):
+        xf = xf.contiguous()
+    if lengths is not None:
+        lengths = lengths.reshape(-1).to(device=wav.device, dtype=torch.int64).contiguous()
+    f0 = torch.empty((N, F), dtype=torch.float32, device=wav.device)
+    ap = torch.empty((N, F), dtype=torch.float32, device=wav.device)
+    lag = torch.empty((N, F), dtype=torch.int32, device=wav.device)
+    if N > 0:
+        with on(wav.device) as hip:
+            hip.psnd_yin_f0(xf if T > 0 else None, N, T, lengths, hop, W, tau_min, tau_max, th, float(sr), f0, ap, lag, F)
+    return f0.reshape(lead + (F,)), ap.reshape(lead + (F,)), lag.reshape(lead + (F,))
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

@@ -18,8 +18,8 @@ Not covered: energies are float64 sums of float32 samples, the reference's are f
 threshold to within float32 rounding may be decided the other way (the golden cases keep a margin of 1e-3 and agree exactly); a
 window's energy is resolved to 2^-52 of the energy of the 1024-sample blocks it touches, so at -inf dB samples below about 1e-8 of their
 loud neighbours in the same block count as zeros; integer sample arrays are read as their float64 values, where the reference's dot
-product wraps around; a per-sample silence mask and pydub's AudioSegment front end are not here, nor are the reference's `get_f0` /
-`parse_midi` helpers of other modules.
+product wraps around; a per-sample silence mask and pydub's AudioSegment front end are not here, nor is the reference's
+`parse_midi` helper of another module (pitch per frame: `utils.pitch`).
 """
 import numpy as np
 

@@ -10,6 +10,7 @@ device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilte
 no host round trip, no library op), on a CPU tensor scipy in float64.  All filters run along the last axis with zero initial state.
 
 Not here: `parse_midi` (pretty_midi) and `get_f0` (pyworld, librosa) - host-only wrappers around packages this project does not depend on.
+A pitch tracker of this project's own - YIN, not WORLD, so under another roof - is `utils.pitch.get_f0`, with the reference's arguments.
 
 `lowpass` is NOT pinned against the reference: its output there is whatever the installed sox computes (through pysndfx), which this
 project cannot run.  What is implemented is the two-pole low-pass of the Audio EQ Cookbook, the design sox documents for its `lowpass`
