@@ -761,6 +761,46 @@ int64_t psnd_yin_max_span(void);
 int psnd_yin_f0(const float *x, int64_t N, int64_t T, const int64_t *lengths, int64_t hop, int64_t W, int64_t tau_min, int64_t tau_max,
                 float threshold, double sr, float *f0, float *aperiodicity, int32_t *lag, int64_t F, void *stream);
 
+/* ---- time-scale modification of a complex spectrogram on device tensors (psnd_phase_vocoder.hip): the phase vocoder between
+ *  STFT.transform_complex and STFT.inverse_complex, what utils.sound.time_stretch / pitch_shift are built on.  The reference reaches such
+ *  effects through pysndfx (sox `tempo` / `pitch`, which is WSOLA); what is computed here is the plain phase vocoder of torchaudio's
+ *  phase_vocoder and librosa's time_stretch - parity with sox is unpinned.
+ *  Inputs.   re, im : fp32 (N, K, F), the frame axis contiguous; X = re + i im.  rate : a double, positive and finite.  frames : one
+ *            int64 per batch item n (device), clamped to [0, F], or NULL for F_n = F everywhere; X[n, k, f] counts as 0 for f >= F_n
+ *            whatever the memory holds (no global read leaves [0, F_n)).
+ *  Per row (n, k) and output frame j = 0, 1, ...:
+ *      t_j = (double) j * rate     one IEEE double multiplication, not fused with what follows
+ *      i_j = floor(t_j),  alpha_j = t_j - i_j
+ *      mag_j = (1 - alpha_j) |X[i_j]| + alpha_j |X[i_j + 1]|
+ *      phi_0 = arg X[0],  phi_j = phi_{j-1} + (arg X[i_{j-1} + 1] - arg X[i_{j-1}]),  arg 0 = 0 (either sign of either zero)
+ *      Y_j = mag_j (cos phi_j, sin phi_j)
+ *  Row n has J_n = psnd_pv_frames(F_n, rate) valid output frames: the number of j >= 0 with (double) j * rate < F_n (counted by that
+ *  wording, not a bare ceil(F / rate)).  Outputs yre, yim : fp32 (N, K, J) with J >= psnd_pv_frames(F, rate); EVERY slot is written, the
+ *  slots of a row from J_n on hold (0, 0).
+ *  Only phi mod 2 pi matters, which makes this the function of the textbook wording (subtract the bin's expected advance
+ *  pi hop k / (K - 1), wrap to [-pi, pi], add it back, cumsum): the expected advance cancels modulo a turn, so neither n_fft nor hop is
+ *  a parameter.
+ *  Freedoms of the implementation: the phase may be accumulated in any way that keeps it to float32 rounding of the single angles over
+ *  rows of any length (fp64, a fixed-point fraction of a turn, renormalised complex products); arg may be avoided altogether.  This one
+ *  takes atan2f of every element it reads, turns each angle into a 64-bit fixed-point fraction of a turn (2^64 = one turn, exact and
+ *  order-independent under integer addition, the modulo is the wrap-around) and sums those.
+ *  Non-finite input.  Rows are independent.  In a row that reads a NaN or an Inf - X[i_j] or X[i_j + 1] of some frame j - every output
+ *  frame from the first such j on is NaN in both parts (through its own mag or through an earlier phase step: a lost phase must not look
+ *  like audio); an element no frame reads (skipped at rate > 1, at or behind F_n) changes nothing; no other row changes by a bit.
+ *  One launch, no scratch, no atomics, no host synchronisation; a fixed order of operations: repeated launches agree bit for bit.  A wave
+ *  walks one row in passes of psnd_pv_pass() = 64 x 4 consecutive output frames (a lane owns 4 consecutive frames: 16-byte stores), an
+ *  in-wave scan of the phase steps with a carry from pass to pass.  Rows are not split (profiles/NOTEBOOK.md has the one-clip figure).
+ *  psnd_pv_pass(): the frames per pass, the one size the kernel's seams depend on (host helper; a function, as psnd_yin_max_span, not
+ *  a macro: the set of macros of this header is pinned by tests/test_cabi.py).
+ *  PSND_E_ARG before anything is launched: rate not positive and finite, N, K or F < 0, J >= 2^31, J < psnd_pv_frames(F, rate), a NULL
+ *      pointer with work to do (re / im may be NULL when F == 0, frames always); more than 2^31 - 1 workgroups: PSND_E_SHAPE.
+ *      N K == 0 or J == 0: PSND_OK, nothing launched.
+ *  psnd_pv_frames(F, rate): host helper, 0 for F <= 0 or a rate that is not positive and finite, INT64_MAX where the count passes 2^53. */
+int64_t psnd_pv_pass(void);
+int64_t psnd_pv_frames(int64_t F, double rate);
+int psnd_phase_vocoder(const float *re, const float *im, int64_t N, int64_t K, int64_t F, const int64_t *frames, double rate, float *yre,
+                       float *yim, int64_t J, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

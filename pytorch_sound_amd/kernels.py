@@ -2,7 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges` and `yin_f0` alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0` and `phase_vocoder` alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
@@ -1605,6 +1605,146 @@ def yin_f0(wav, hop, sr=22050, f0_floor=71.0, f0_ceil=800.0, threshold=0.1, fram
         with on(wav.device) as hip:
             hip.psnd_yin_f0(xf if T > 0 else None, N, T, lengths, hop, W, tau_min, tau_max, th, float(sr), f0, ap, lag, F)
     return f0.reshape(lead + (F,)), ap.reshape(lead + (F,)), lag.reshape(lead + (F,))
+
+
+def pv_pass():
+    """psnd_pv_pass: the output frames a wave of psnd_phase_vocoder.hip takes per pass - the size its seams depend on"""
+    return int(lib().psnd_pv_pass())
+
+
+def _pv_rate(rate):
+    try:
+        r = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError('phase_vocoder: rate=%r - a positive, finite number' % (rate,))
+    if isinstance(rate, bool) or not (r > 0.0 and math.isfinite(r)):
+        raise ValueError('phase_vocoder: rate=%r - a positive, finite number' % (rate,))
+    return r
+
+
+def pv_frames(F, rate):
+    """psnd_pv_frames: the number of output frames j >= 0 with float(j) * rate < F, counted by that wording (a bare ceil(F / rate) is off
+    by one where the product rounds)"""
+    F, rate = int(F), _pv_rate(rate)
+    if F <= 0:
+        return 0
+    q = math.ceil(F / rate)
+    if q >= 2 ** 53:
+        raise ValueError('phase_vocoder: F=%d at rate=%r is more than 2^53 output frames' % (F, rate))
+    j = int(q)
+    while j > 0 and not float(j - 1) * rate < F:
+        j -= 1
+    while float(j) * rate < F:
+        j += 1
+    return j
+
+
+def pitch_ratio(n_steps, bins_per_octave=12):
+    """(p, q): the fraction p / q closest in cents to 2 ** (n_steps / bins_per_octave) with max(p, q) <= 640 - the largest factor whose
+    default resampling filter (20 max + 1 taps) fits RESAMPLE_MAX_TAPS -, ties to the smaller p.  utils.sound.pitch_shift shifts by THIS
+    interval, not the irrational one; every semitone count up to an octave is met within 0.03 cent."""
+    n, b = float(n_steps), float(bins_per_octave)
+    if not math.isfinite(n) or not (b > 0.0 and math.isfinite(b)) or isinstance(bins_per_octave, bool):
+        raise ValueError('pitch_ratio: n_steps=%r bins_per_octave=%r - a finite count of steps, a positive count per octave' % (n_steps, bins_per_octave))
+    octaves = n / b
+    top = (RESAMPLE_MAX_TAPS - 1) // 20
+    if abs(octaves) > math.log2(top):
+        raise ValueError('pitch_ratio: %r steps of %r per octave is beyond a factor of %d' % (n_steps, bins_per_octave, top))
+    target = 2.0 ** octaves
+    best, best_err = (1, 1), abs(octaves)
+    for p in range(1, top + 1):
+        q0 = p / target
+        for q in (math.floor(q0), math.floor(q0) + 1):
+            if 1 <= q <= top:
+                err = abs(math.log2(p / q) - octaves)
+                if err < best_err:
+                    best, best_err = (p, q), err
+    g = math.gcd(*best)
+    return best[0] // g, best[1] // g
+
+
+def phase_vocoder_host(re, im, rate, frames=None):
+    """the definition of include/psnd.h on float64 numpy arrays (..., F), vectorised over the rows and the output frames: (yre, yim), each
+    (..., pv_frames(F, rate)).  `frames`: valid input frames per row of the arrays flattened to (rows, F) - one entry per row, or anything
+    that broadcasts against the leading axes -, clamped to [0, F]."""
+    rate = _pv_rate(rate)
+    re, im = np.asarray(re, dtype=np.float64), np.asarray(im, dtype=np.float64)
+    if re.shape != im.shape or re.ndim == 0:
+        raise ValueError('phase_vocoder: re %s and im %s must have one shape with a frame axis' % (re.shape, im.shape))
+    lead, F = re.shape[:-1], re.shape[-1]
+    J = pv_frames(F, rate)
+    Fn = np.full(lead, F, dtype=np.int64) if frames is None else np.clip(np.broadcast_to(np.asarray(frames, dtype=np.int64), lead), 0, F)
+    live = np.arange(F + 1) < Fn[..., None]                                  # one frame of zeros behind the row
+    xr = np.where(live, np.concatenate((re, np.zeros(lead + (1,))), axis=-1), 0.0)
+    xi = np.where(live, np.concatenate((im, np.zeros(lead + (1,))), axis=-1), 0.0)
+    t = np.arange(J, dtype=np.float64) * rate
+    i = np.floor(t).astype(np.int64)
+    alpha = t - i
+    with np.errstate(invalid='ignore', over='ignore'):
+        mag = np.hypot(xr, xi)
+        ang = np.where((xr == 0.0) & (xi == 0.0), 0.0, np.arctan2(xi, xr))
+        lost = ~(np.isfinite(xr) & np.isfinite(xi))
+        step = ang[..., i + 1] - ang[..., i]
+        phi = ang[..., :1] + np.concatenate((np.zeros(lead + (min(J, 1),)), np.cumsum(step[..., :-1], axis=-1)), axis=-1)
+        m = (1.0 - alpha) * mag[..., i] + alpha * mag[..., i + 1]
+        yre, yim = m * np.cos(phi), m * np.sin(phi)
+    nan = np.logical_or.accumulate(lost[..., i] | lost[..., i + 1], axis=-1)
+    valid = t < Fn[..., None]
+    yre = np.where(valid, np.where(nan, np.nan, yre), 0.0)
+    yim = np.where(valid, np.where(nan, np.nan, yim), 0.0)
+    return yre, yim
+
+
+def phase_vocoder(re, im, rate, frames=None):
+    """time-scale modification of the spectrogram re + i im, tensors (..., K, F) as STFT.transform_complex returns them, by the definition
+    of include/psnd.h: output frame j stands at the input time j rate, its magnitude interpolated between the frames floor(j rate) and
+    floor(j rate) + 1, its phase advanced by the angle between the two frames the frame before it read.  Returns (yre, yim), each
+    (..., K, pv_frames(F, rate)) in the inputs' dtype and on their device.  rate > 1 shortens, rate < 1 lengthens.  `frames`: valid input
+    frames per batch item (one integer per leading index, clamped to [0, F]); an item's frames from there on count as zeros and its output
+    slots from pv_frames(frames[n], rate) on hold zeros.  A row that reads a NaN or an Inf is NaN from that output frame on.
+
+    HIP tensors run psnd_phase_vocoder (float32; float16 / bfloat16 are cast in and out; float64 raises) in one launch with no host
+    synchronisation - the call can be captured; `frames` is then an int64 tensor on the same device (anything else is copied there).  CPU
+    tensors go through phase_vocoder_host in float64.  No autograd: the outputs carry no graph, gradients are out of scope."""
+    if not isinstance(re, torch.Tensor) or not isinstance(im, torch.Tensor):
+        raise _lib.PsndError('phase_vocoder: tensors are expected, got %s and %s' % (type(re).__name__, type(im).__name__))
+    if re.shape != im.shape or re.dtype != im.dtype or re.device != im.device:
+        raise _lib.PsndError('phase_vocoder: re (%s %s %s) and im (%s %s %s) must agree' % (tuple(re.shape), re.dtype, re.device, tuple(im.shape),
+                                                                                          im.dtype, im.device))
+    if re.dim() < 2:
+        raise _lib.PsndError('phase_vocoder: (..., K, F) expected, got %s' % (tuple(re.shape),))
+    if not re.is_floating_point():
+        raise _lib.PsndError('phase_vocoder: floating input expected, got %s' % re.dtype)
+    rate = _pv_rate(rate)
+    lead, K, F = tuple(re.shape[:-2]), re.shape[-2], re.shape[-1]
+    N = math.prod(lead)
+    J = pv_frames(F, rate)
+    if J >= 2 ** 31:
+        raise _lib.PsndError('phase_vocoder: F=%d at rate=%r is %d output frames, 2^31 or more' % (F, rate, J))
+    if frames is not None:
+        frames = torch.as_tensor(frames)
+        if frames.is_floating_point() or frames.numel() != N:
+            raise _lib.PsndError('phase_vocoder: frames must be %d integers, got %s %s' % (N, tuple(frames.shape), frames.dtype))
+    out_shape = lead + (K, J)
+    if not re.is_cuda:
+        fr = None if frames is None else frames.reshape(N, 1).numpy()
+        yr, yi = phase_vocoder_host(re.detach().reshape(N, K, F).to(torch.float64).numpy(), im.detach().reshape(N, K, F).to(torch.float64).numpy(),
+                                    rate, fr)
+        return tuple(torch.from_numpy(np.ascontiguousarray(y)).to(re.dtype).reshape(out_shape) for y in (yr, yi))
+    if re.dtype == torch.float64:
+        raise _lib.PsndError('phase_vocoder: no float64 instance on HIP tensors (a round trip through float32 would silently lose the '
+                             'precision asked for): pass float32 tensors, or CPU tensors in float64')
+    if re.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.PsndError('phase_vocoder: floating input expected, got %s' % re.dtype)
+    xr, xi = (t.detach().reshape(N, K, F).float().contiguous() for t in (re, im))
+    if frames is not None:
+        frames = frames.reshape(-1).to(device=re.device, dtype=torch.int64).contiguous()
+    yr = torch.empty((N, K, J), dtype=torch.float32, device=re.device)
+    yi = torch.empty((N, K, J), dtype=torch.float32, device=re.device)
+    if N * K * J > 0:
+        with on(re.device) as hip:
+            hip.psnd_phase_vocoder(xr if F > 0 else None, xi if F > 0 else None, N, K, F, frames, rate, yr, yi, J)
+    return yr.to(re.dtype).reshape(out_shape), yi.to(re.dtype).reshape(out_shape)
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

@@ -1,5 +1,5 @@
 """Drop-in for pytorch_sound/models/sound.py: VolNormConv, PreEmphasis, InversePreEmphasis, build_stft_functions,
-multi_stft_loss - same names, arguments and results - and Resample, which the reference does not have.
+multi_stft_loss - same names, arguments and results - and Resample, TimeStretch and PitchShift, which the reference does not have.
 
 On a HIP device every class here runs on libpsnd_hip.so (psnd_volnorm_*, psnd_preemphasis_*, psnd_ipreemph_*, psnd_stft_fwd/bwd,
 psnd_stft_loss_*); CPU tensors take the reference's torch formulation (host-side use: tests, data preparation).
@@ -174,6 +174,53 @@ class Resample(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return 'orig_sr=%d, new_sr=%d, up=%d, down=%d' % (self.orig_sr, self.new_sr, self.up, self.down)
+
+
+def _wave_rows(wav: torch.Tensor, who: str) -> torch.Tensor:
+    if wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.size(1) != 1):
+        raise RuntimeError('%s expects a (B, T) or (B, 1, T) tensor, got %s' % (who, tuple(wav.shape)))
+    return wav
+
+
+class TimeStretch(torch.nn.Module):
+    """``utils.sound.time_stretch`` as a module on (B, T) or (B, 1, T), no parameters: 1 / ``rate`` times as long at unchanged pitch,
+    int(round(T / rate)) samples out.  The plain phase vocoder (include/psnd.h), not sox's ``tempo``; parity unpinned.  The module owns
+    its STFT, whose plan is cached per device: after a first call a call copies nothing from the host and can be captured.  No gradient."""
+
+    def __init__(self, rate: float, n_fft: int = 1024, hop_length: int = 256):
+        super().__init__()
+        from pytorch_sound_amd.models.transforms import STFT as ConvSTFT
+        self.rate = K._pv_rate(rate)
+        self.stft = ConvSTFT(n_fft, hop_length)
+
+    def forward(self, wav: torch.Tensor) -> torch.Tensor:
+        from pytorch_sound_amd.utils import sound as U
+        return U._effect(lambda rows: U.stretch_rows(rows, self.rate, self.stft), _wave_rows(wav, 'TimeStretch'), 'TimeStretch')
+
+    def extra_repr(self) -> str:
+        return 'rate=%r, n_fft=%d, hop_length=%d' % (self.rate, self.stft.filter_length, self.stft.hop_length)
+
+
+class PitchShift(torch.nn.Module):
+    """``utils.sound.pitch_shift`` as a module on (B, T) or (B, 1, T), no parameters: ``n_steps`` steps of an octave /
+    ``bins_per_octave`` up (negative: down) at unchanged length; the interval is the fraction ``K.pitch_ratio`` picks.  Not sox's ``pitch``;
+    parity unpinned.  Owns its STFT and, as ``Resample`` does, the float32 resampling taps as a non-persistent buffer.  No gradient."""
+
+    def __init__(self, sr: int, n_steps: float, bins_per_octave: int = 12, n_fft: int = 1024, hop_length: int = 256):
+        super().__init__()
+        from pytorch_sound_amd.models.transforms import STFT as ConvSTFT
+        self.sr, self.n_steps, self.bins_per_octave = sr, n_steps, bins_per_octave
+        self.p, self.q = K.pitch_ratio(n_steps, bins_per_octave)
+        self.stft = ConvSTFT(n_fft, hop_length)
+        self.register_buffer('taps', torch.from_numpy(K.resample_taps(self.q, self.p)).float(), persistent=False)
+
+    def forward(self, wav: torch.Tensor) -> torch.Tensor:
+        from pytorch_sound_amd.utils import sound as U
+        taps = self.taps if wav.is_cuda else None
+        return U._effect(lambda rows: U.shift_rows(rows, (self.p, self.q), self.stft, taps), _wave_rows(wav, 'PitchShift'), 'PitchShift')
+
+    def extra_repr(self) -> str:
+        return 'sr=%r, n_steps=%r, bins_per_octave=%r, p=%d, q=%d' % (self.sr, self.n_steps, self.bins_per_octave, self.p, self.q)
 
 
 #

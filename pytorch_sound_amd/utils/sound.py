@@ -4,6 +4,8 @@
     lowpass, highpass, biquad      two-pole sections (the reference's lowpass pipes the array through sox, :25-35)
     get_wav_duration               :52-63
     resample                       sample-rate conversion (the reference shells out: scripts/preprocess.py:82-88 sox, :32-41 ffmpeg)
+    time_stretch, pitch_shift      duration without pitch and pitch without duration (the reference reaches sox's `tempo` / `pitch` through
+                                   pysndfx's AudioEffectsChain)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -23,6 +25,15 @@ depends through scipy: with up / down = new_sr / orig_sr in lowest terms and P =
 firwin(2P + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up applied between zero-stuffing by `up` and keeping every `down`-th sample,
 zeros beyond both ends, ceil(T up / down) samples out.  A numpy array goes through scipy itself; a HIP tensor through the polyphase kernel of
 psnd_resample.hip (`kernels.resample_poly`), which is that sum in float32 and whose gradient is the same kernel the other way round.
+
+`time_stretch` and `pitch_shift` are NOT pinned against the reference either: parity with sox's `tempo` and `pitch` is UNPINNED.  sox
+changes the time scale by WSOLA (overlap-add of waveform segments picked by correlation); what is implemented here is the plain phase
+vocoder of torchaudio's `phase_vocoder` and librosa's `time_stretch` / `pitch_shift`, by the definition written out in include/psnd.h:
+STFT, output frame j at the input time j rate with an interpolated magnitude and an accumulated phase advance, inverse STFT; the pitch
+shift is that stretch followed by `resample_poly` with the fraction `kernels.pitch_ratio` picks.  On a HIP tensor all three steps are
+native (`STFT.transform_complex`, psnd_phase_vocoder.hip, `psnd_istft_reim`; the phase is summed as a fixed-point fraction of a turn, so
+a long clip keeps it); numpy arrays and CPU tensors run the same definition in float64 numpy between the host STFTs.  No transient or
+formant handling, no phase locking, no gradient.
 """
 import math
 
@@ -101,6 +112,86 @@ def resample(wav, orig_sr, new_sr):
     if wav.size == 0:
         return np.zeros(wav.shape[:-1] + (-(-wav.shape[-1] * up // down),), dtype=np.float32)
     return signal.resample_poly(wav.astype(np.float64), up, down, axis=-1).astype(np.float32)
+
+
+_STFTS = {}
+
+
+def _stft(n_fft, hop_length):
+    """one STFT module per (n_fft, hop_length): its plans are cached per device, so a later call copies nothing from the host"""
+    from ..models.transforms import STFT
+    key = (int(n_fft), int(hop_length))
+    if key not in _STFTS:
+        if key[0] < 2 or key[1] < 1:
+            raise ValueError('time_stretch: n_fft=%r hop_length=%r' % (n_fft, hop_length))
+        _STFTS[key] = STFT(key[0], key[1])
+    return _STFTS[key]
+
+
+def _fix_length(y, n):
+    """the last axis trimmed or zero-padded to n samples"""
+    import torch
+    if y.shape[-1] >= n:
+        return y[..., :n].contiguous()
+    return torch.nn.functional.pad(y, (0, n - y.shape[-1]))
+
+
+def _effect(fn, wav, what):
+    """numpy in -> float32 numpy out through the CPU path; tensor in -> tensor of the same dtype and device out, no graph.  fn takes and
+    returns (N, T) rows in float32 (float64 stays float64 on the CPU; on a HIP tensor it raises)."""
+    import torch
+    if not _is_tensor(wav):
+        x = np.asarray(wav)
+        if x.ndim == 0:
+            raise kernels.PsndError('%s: the input needs a time axis' % what)
+        return _effect(fn, torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), what).numpy()
+    if wav.dim() == 0:
+        raise kernels.PsndError('%s: the input needs a time axis' % what)
+    if not wav.is_floating_point():
+        raise kernels.PsndError('%s: floating input expected, got %s' % (what, wav.dtype))
+    if wav.is_cuda and wav.dtype == torch.float64:
+        raise kernels.PsndError('%s: no float64 instance on HIP tensors: pass a float32 tensor, or a CPU tensor in float64' % what)
+    with torch.no_grad():
+        rows = wav.detach().reshape(-1, wav.shape[-1])
+        y = fn(rows if rows.dtype == torch.float64 else rows.float())
+    return y.to(wav.dtype).reshape(wav.shape[:-1] + (y.shape[-1],))
+
+
+def stretch_rows(rows, rate, stft):
+    """(N, T) -> (N, round(T / rate)): stft.transform_complex, kernels.phase_vocoder, stft.inverse_complex, trimmed or zero-padded"""
+    re, im = stft.transform_complex(rows)
+    yr, yi = kernels.phase_vocoder(re, im, rate)
+    return _fix_length(stft.inverse_complex(yr, yi), int(round(rows.shape[-1] / rate)))
+
+
+def shift_rows(rows, ratio, stft, device_taps=None):
+    """(N, T) -> (N, T): stretched by q / p, then resampled by q / p, for ratio = (p, q) = kernels.pitch_ratio(...)"""
+    p, q = ratio
+    y = stretch_rows(rows, q / p, stft)
+    return _fix_length(kernels.resample_poly(y, q, p, device_taps=device_taps), rows.shape[-1])
+
+
+def time_stretch(wav, rate, n_fft=1024, hop_length=256):
+    """`wav` (..., T) made 1 / rate times as long without changing its pitch (rate > 1: faster and shorter), int(round(T / rate))
+    samples out (librosa's rule): STFT(n_fft, hop_length).transform_complex, kernels.phase_vocoder, inverse_complex.  The plain phase
+    vocoder of torchaudio / librosa, no transient handling; not sox's `tempo` (WSOLA) - module docstring.  T must exceed n_fft / 2
+    (the transform's reflect padding).  numpy in -> float32 numpy out; tensor in -> tensor of the same dtype and device out.  No gradient."""
+    rate = kernels._pv_rate(rate)
+    stft = _stft(n_fft, hop_length)
+    return _effect(lambda rows: stretch_rows(rows, rate, stft), wav, 'time_stretch')
+
+
+def pitch_shift(wav, sr, n_steps, bins_per_octave=12, n_fft=1024, hop_length=256):
+    """`wav` (..., T) shifted by `n_steps` steps of an octave / `bins_per_octave` at unchanged length T (librosa's arguments; `sr` does not
+    enter): with (p, q) = kernels.pitch_ratio(n_steps, bins_per_octave), resample_poly(time_stretch(wav, q / p), up=q, down=p), trimmed or
+    zero-padded to T.  The interval is the fraction p / q (max(p, q) <= 640, within 0.03 cent of the semitones up to an octave), not the
+    irrational 2 ** (n_steps / bins_per_octave).  Not sox's `pitch` - module docstring.  numpy in -> float32 numpy out; tensor in ->
+    tensor of the same dtype and device out.  No gradient."""
+    if not float(sr) > 0.0:
+        raise ValueError('pitch_shift: sr=%r must be positive' % (sr,))
+    ratio = kernels.pitch_ratio(n_steps, bins_per_octave)
+    stft = _stft(n_fft, hop_length)
+    return _effect(lambda rows: shift_rows(rows, ratio, stft), wav, 'pitch_shift')
 
 
 def get_wav_duration(file):
