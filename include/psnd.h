@@ -801,6 +801,54 @@ int64_t psnd_pv_frames(int64_t F, double rate);
 int psnd_phase_vocoder(const float *re, const float *im, int64_t N, int64_t K, int64_t F, const int64_t *frames, double rate, float *yre,
                        float *yim, int64_t J, void *stream);
 
+/* ---- Griffin-Lim on device tensors (psnd_griffinlim.hip): a waveform from a magnitude spectrogram alone, what kernels.griffinlim,
+ *  utils.sound.griffinlim and models.sound.GriffinLim are built on.  The definition is torchaudio's functional.griffinlim and librosa's
+ *  griffinlim - the fast Griffin-Lim of Perraudin, Balazs and Sondergaard (2013) - on this project's STFT.transform_complex /
+ *  inverse_complex.  The reference has no such function: there is no parity to pin.  The two entry points below are the start of the loop
+ *  and the phase step between the two transforms; the loop itself lives in kernels.griffinlim.
+ *  Inputs.   S = mag : fp32 (N, K, F), the frame axis contiguous, elements e = k F + f of item n at n K F + e.  alpha = momentum /
+ *            (1 + momentum) and eps (the loop passes 1e-16) : floats by value.  frames : one int64 per batch item n (device), clamped to
+ *            [0, F], or NULL for F_n = F everywhere.
+ *  Start.    X0 = S (cos phi, sin phi) for a phase tensor phi of S's shape; X0 = (S, +0) when phi is NULL.
+ *  Each of n_iter iterations.
+ *      y = inverse_complex(X),  C = transform_complex(y)
+ *      t = C - alpha P   componentwise, P the C of the iteration before; in the first iteration (pre and pim NULL) t = C
+ *      r = hypot(t_re, t_im)
+ *      X = S (t / (r + eps))    the quotient first, then the product with S: |t| near 1e30 does not overflow, t = 0 gives exactly (0, 0),
+ *                               and so does S = 0 wherever the quotient is finite
+ *      then P = C
+ *  End.      y = inverse_complex(X): (F - 1) hop samples.
+ *  Ragged items.  Elements at f >= F_n are written as (+0, +0) by both entry points and are never read, whatever the memory holds - of no
+ *  input plane.
+ *  Convergence measure (optional).  conv[i, n] = sqrt(sum (|C| - S)^2 / sum S^2) over the valid elements of item n in iteration i, 0
+ *  where the denominator is 0.  The step writes, when `partial` is given, one pair of fp32 sums per chunk: partial is
+ *  (N, psnd_gl_chunks(K, F), 2) with [n, c, 0] = sum (hypot(C_re, C_im) - S)^2 and [n, c, 1] = sum S^2 over the valid elements
+ *  c psnd_gl_chunk() <= e < (c + 1) psnd_gl_chunk() of item n (a chunk belongs to one item; a chunk without valid elements holds (0, 0)).
+ *  The caller adds the pairs up (kernels.griffinlim: in float64, once, after the last iteration).
+ *  Non-finite input: no special rule; it propagates as IEEE arithmetic gives.
+ *  Freedoms of the implementation: a fused or unfused multiply-add in t; the device library's hypotf (and sincosf in the start).
+ *  Everything else - the subtraction order, the addition of eps, the IEEE division, the product - is as written.  This implementation
+ *  takes t = fmaf(-alpha, P, C).
+ *  One launch each, no atomics, no scratch beyond `partial`, no host synchronisation; a fixed order of operations: repeated launches agree
+ *  bit for bit, `partial` included (a lane adds its elements in ascending order, the lanes of a wave are added by a shuffle tree, the waves of
+ *  a workgroup in ascending order).  A workgroup takes one chunk of psnd_gl_chunk() consecutive elements of one item; a lane owns groups of
+ *  4 consecutive elements (16-byte loads and stores where the address allows; any 4-byte alignment and any K F are served, a group that
+ *  crosses the end of a ragged row or of the item goes element by element).  Five planes read, two written: 28 N K F bytes per step.
+ *  Aliasing: xre / xim may be the very buffers pre / pim (each element is read before the lane that owns it writes it); no other two
+ *  arguments may overlap.
+ *  psnd_gl_chunk(): the elements per workgroup, the one size the kernel's seams depend on (host helper; a function, as psnd_pv_pass, not a
+ *  macro: the set of macros of this header is pinned by tests/test_cabi.py).  psnd_gl_chunks(K, F): the chunks per item,
+ *  ceil(K F / psnd_gl_chunk()); 0 for K <= 0 or F <= 0.
+ *  PSND_E_ARG before anything is launched: N, K or F < 0, exactly one of pre / pim NULL, a NULL pointer with work to do (phase, frames,
+ *      partial and the pair pre / pim may be NULL always).  PSND_E_SHAPE: K F >= 2^31, or more than 2^31 - 1 workgroups.
+ *      N K F == 0: PSND_OK, nothing launched, no pointer looked at. */
+int64_t psnd_gl_chunk(void);
+int64_t psnd_gl_chunks(int64_t K, int64_t F);
+int psnd_griffinlim_start(const float *mag, const float *phase, int64_t N, int64_t K, int64_t F, const int64_t *frames, float *xre,
+                          float *xim, void *stream);
+int psnd_griffinlim_step(const float *mag, const float *cre, const float *cim, const float *pre, const float *pim, int64_t N, int64_t K,
+                         int64_t F, const int64_t *frames, float alpha, float eps, float *xre, float *xim, float *partial, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

@@ -2,7 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0` and `phase_vocoder` alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder` and the `griffinlim*` functions alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
@@ -1745,6 +1745,247 @@ def phase_vocoder(re, im, rate, frames=None):
         with on(re.device) as hip:
             hip.psnd_phase_vocoder(xr if F > 0 else None, xi if F > 0 else None, N, K, F, frames, rate, yr, yi, J)
     return yr.to(re.dtype).reshape(out_shape), yi.to(re.dtype).reshape(out_shape)
+
+
+GL_EPS = 1e-16
+
+
+def gl_chunk():
+    """psnd_gl_chunk: the elements of an item a workgroup of psnd_griffinlim.hip takes - the size its seams depend on"""
+    return int(lib().psnd_gl_chunk())
+
+
+def gl_chunks(K, F):
+    """psnd_gl_chunks: the chunks per item, ceil(K F / gl_chunk()) - the middle axis of the step's `partial`"""
+    return int(lib().psnd_gl_chunks(int(K), int(F)))
+
+
+def _gl_host_frames(frames, N, F):
+    if frames is None:
+        return np.full((N,), F, dtype=np.int64)
+    return np.clip(np.asarray(frames, dtype=np.int64).reshape(N), 0, F)
+
+
+def griffinlim_start_host(mag, phase=None, frames=None):
+    """the start of include/psnd.h's Griffin-Lim section on float64 numpy arrays (N, K, F): X0 = S (cos phi, sin phi), (S, 0) without a
+    phase, (0, 0) at f >= frames[n]"""
+    S = np.asarray(mag, dtype=np.float64)
+    if S.ndim != 3:
+        raise ValueError('griffinlim_start: (N, K, F) expected, got %s' % (S.shape,))
+    N, _, F = S.shape
+    live = np.arange(F)[None, None, :] < _gl_host_frames(frames, N, F)[:, None, None]
+    if phase is None:
+        return np.where(live, S, 0.0), np.zeros_like(S)
+    phi = np.asarray(phase, dtype=np.float64)
+    if phi.shape != S.shape:
+        raise ValueError('griffinlim_start: mag %s and phase %s must have one shape' % (S.shape, phi.shape))
+    with np.errstate(invalid='ignore', over='ignore'):
+        return np.where(live, S * np.cos(phi), 0.0), np.where(live, S * np.sin(phi), 0.0)
+
+
+def griffinlim_step_host(mag, cre, cim, pre=None, pim=None, alpha=0.0, eps=GL_EPS, frames=None):
+    """the step of include/psnd.h's Griffin-Lim section on float64 numpy arrays (N, K, F): t = C - alpha P (t = C without P),
+    X = S (t / (hypot(t) + eps)), (0, 0) at f >= frames[n].  Returns (xre, xim, sums) with sums (N, 2) = the sums of (|C| - S)^2 and of S^2
+    over the valid elements of each item."""
+    S, cr, ci = (np.asarray(a, dtype=np.float64) for a in (mag, cre, cim))
+    if S.ndim != 3 or cr.shape != S.shape or ci.shape != S.shape:
+        raise ValueError('griffinlim_step: mag, cre, cim must share one (N, K, F) shape, got %s %s %s' % (S.shape, cr.shape, ci.shape))
+    if (pre is None) != (pim is None):
+        raise ValueError('griffinlim_step: pre and pim come together or not at all')
+    N, _, F = S.shape
+    live = np.arange(F)[None, None, :] < _gl_host_frames(frames, N, F)[:, None, None]
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        tr, ti = cr, ci
+        if pre is not None:
+            pr, pi = np.asarray(pre, dtype=np.float64), np.asarray(pim, dtype=np.float64)
+            if pr.shape != S.shape or pi.shape != S.shape:
+                raise ValueError('griffinlim_step: pre %s and pim %s must have the shape of mag %s' % (pr.shape, pi.shape, S.shape))
+            tr, ti = cr - alpha * pr, ci - alpha * pi
+        den = np.hypot(tr, ti) + eps
+        xr = np.where(live, S * (tr / den), 0.0)
+        xi = np.where(live, S * (ti / den), 0.0)
+        d = np.where(live, np.hypot(cr, ci) - S, 0.0)
+        q = np.where(live, S, 0.0)
+        sums = np.stack(((d * d).sum(axis=(1, 2)), (q * q).sum(axis=(1, 2))), axis=-1)
+    return xr, xi, sums
+
+
+def _gl_planes(who, named, frames):
+    """shape, dtype and device checks shared by griffinlim_start / griffinlim_step: `named` = [(name, tensor or None)], the first one is
+    the magnitude.  Returns (lead, N, K, F, frames as they go to the entry point)"""
+    first = named[0][1]
+    for name, t in named:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise _lib.PsndError('%s: tensors are expected, %s is a %s' % (who, name, type(t).__name__))
+        if t.shape != first.shape or t.dtype != first.dtype or t.device != first.device:
+            raise _lib.PsndError('%s: %s (%s %s %s) must agree with %s (%s %s %s)' % (who, name, tuple(t.shape), t.dtype, t.device, named[0][0],
+                                                                                    tuple(first.shape), first.dtype, first.device))
+    if first.dim() < 2:
+        raise _lib.PsndError('%s: (..., K, F) expected, got %s' % (who, tuple(first.shape)))
+    if not first.is_floating_point():
+        raise _lib.PsndError('%s: floating input expected, got %s' % (who, first.dtype))
+    if first.is_cuda and first.dtype == torch.float64:
+        raise _lib.PsndError('%s: no float64 instance on HIP tensors (a round trip through float32 would silently lose the precision asked '
+                             'for): pass float32 tensors, or CPU tensors in float64' % who)
+    if first.is_cuda and first.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise _lib.PsndError('%s: floating input expected, got %s' % (who, first.dtype))
+    lead, K, F = tuple(first.shape[:-2]), first.shape[-2], first.shape[-1]
+    N = math.prod(lead)
+    if frames is not None:
+        frames = torch.as_tensor(frames)
+        if frames.is_floating_point() or frames.dtype == torch.bool or frames.numel() != N:
+            raise _lib.PsndError('%s: frames must be %d integers, got %s %s' % (who, N, tuple(frames.shape), frames.dtype))
+        frames = frames.reshape(-1).to(device=first.device, dtype=torch.int64).contiguous()
+    return lead, N, K, F, frames
+
+
+def _gl_out(who, out, N, K, F, device):
+    if out is None:
+        return (torch.empty((N, K, F), dtype=torch.float32, device=device), torch.empty((N, K, F), dtype=torch.float32, device=device))
+    for t in out:
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.numel() == N * K * F and t.is_contiguous()):
+            raise _lib.PsndError('%s: out must be two contiguous float32 tensors of %d elements on %s' % (who, N * K * F, device))
+    return out
+
+
+def griffinlim_start(mag, phase=None, frames=None):
+    """X0 of Griffin-Lim (include/psnd.h): (xre, xim) = mag (cos phase, sin phase), or (mag, 0) without a phase, tensors (..., K, F) in
+    mag's dtype and on its device; `frames`: valid frames per batch item (one integer per leading index, clamped to [0, F]) - an item's
+    elements from there on are never read and come out as (0, 0).  HIP tensors run psnd_griffinlim_start (float32; float16 / bfloat16 are cast
+    in and out; float64 raises) in one launch; CPU tensors go through griffinlim_start_host in float64.  No autograd."""
+    lead, N, K, F, frames = _gl_planes('griffinlim_start', [('mag', mag), ('phase', phase)], frames)
+    if not mag.is_cuda:
+        fr = None if frames is None else frames.numpy()
+        xr, xi = griffinlim_start_host(mag.detach().reshape(N, K, F).to(torch.float64).numpy(),
+                                       None if phase is None else phase.detach().reshape(N, K, F).to(torch.float64).numpy(), fr)
+        return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(mag.dtype).reshape(mag.shape) for x in (xr, xi))
+    S = mag.detach().reshape(N, K, F).float().contiguous()
+    phi = None if phase is None else phase.detach().reshape(N, K, F).float().contiguous()
+    xr, xi = _gl_out('griffinlim_start', None, N, K, F, mag.device)
+    if N * K * F > 0:
+        with on(mag.device) as hip:
+            hip.psnd_griffinlim_start(S, phi, N, K, F, frames, xr, xi)
+    return xr.to(mag.dtype).reshape(mag.shape), xi.to(mag.dtype).reshape(mag.shape)
+
+
+def griffinlim_step(mag, cre, cim, pre=None, pim=None, alpha=0.0, eps=GL_EPS, frames=None, out=None, partial=False):
+    """one phase step of Griffin-Lim (include/psnd.h): with t = (cre, cim) - alpha (pre, pim) - or t = (cre, cim) without pre / pim -
+    (xre, xim) = mag (t / (hypot(t) + eps)), tensors (..., K, F) in mag's dtype and on its device.  `frames` as in griffinlim_start.
+    `partial=True` also returns the sums of (|C| - mag)^2 and mag^2 over the valid elements: on HIP tensors the kernel's own
+    (N, gl_chunks(K, F), 2) float32 tensor of per-chunk sums (a float32 tensor of that shape may be passed instead and is written), on CPU
+    tensors one float64 pair per item, (N, 1, 2).
+
+    HIP tensors run psnd_griffinlim_step (float32; float16 / bfloat16 are cast in and out; float64 raises; non-contiguous input is made
+    contiguous) in one launch with no host synchronisation - the call can be captured.  `out`: two contiguous float32 tensors of the input's
+    size to write into (float32 input only); they may be the very tensors pre / pim, nothing else of the input.  CPU tensors go through
+    griffinlim_step_host in float64.  No autograd."""
+    who = 'griffinlim_step'
+    if (pre is None) != (pim is None):
+        raise _lib.PsndError('%s: pre and pim come together or not at all' % who)
+    lead, N, K, F, frames = _gl_planes(who, [('mag', mag), ('cre', cre), ('cim', cim), ('pre', pre), ('pim', pim)], frames)
+    alpha, eps = float(alpha), float(eps)
+    if not mag.is_cuda:
+        if out is not None:
+            raise _lib.PsndError('%s: out is for HIP tensors' % who)
+        f64 = lambda t: None if t is None else t.detach().reshape(N, K, F).to(torch.float64).numpy()       # noqa: E731
+        xr, xi, sums = griffinlim_step_host(f64(mag), f64(cre), f64(cim), f64(pre), f64(pim), alpha, eps, None if frames is None else frames.numpy())
+        res = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(mag.dtype).reshape(mag.shape) for x in (xr, xi))
+        return res + (torch.from_numpy(sums).reshape(N, 1, 2),) if partial is not False and partial is not None else res
+    if out is not None and mag.dtype != torch.float32:
+        raise _lib.PsndError('%s: out goes with float32 input, got %s' % (who, mag.dtype))
+    f32 = lambda t: None if t is None else t.detach().reshape(N, K, F).float().contiguous()                  # noqa: E731
+    S, cr, ci, pr, pi = f32(mag), f32(cre), f32(cim), f32(pre), f32(pim)
+    xr, xi = _gl_out(who, out, N, K, F, mag.device)
+    part = None
+    if isinstance(partial, torch.Tensor):
+        part = partial
+        if part.dtype != torch.float32 or part.device != mag.device or not part.is_contiguous() or tuple(part.shape) != (N, gl_chunks(K, F), 2):
+            raise _lib.PsndError('%s: partial must be a contiguous float32 (%d, %d, 2) tensor on %s' % (who, N, gl_chunks(K, F), mag.device))
+    elif partial:
+        part = torch.empty((N, gl_chunks(K, F), 2), dtype=torch.float32, device=mag.device)
+    if N * K * F > 0:
+        with on(mag.device) as hip:
+            hip.psnd_griffinlim_step(S, cr, ci, pr, pi, N, K, F, frames, alpha, eps, xr, xi, part)
+    res = (xr.reshape(mag.shape), xi.reshape(mag.shape)) if out is not None else (xr.to(mag.dtype).reshape(mag.shape), xi.to(mag.dtype).reshape(mag.shape))
+    return res + (part,) if part is not None else res
+
+
+def _gl_convergence(parts):
+    """conv[i, n] = sqrt(sum (|C| - S)^2 / sum S^2) from the stacked sums (n_iter, N, chunks, 2), added up in float64; 0 where S is 0"""
+    sums = parts.double().sum(dim=2)
+    num, den = sums[..., 0], sums[..., 1]
+    return torch.where(den > 0, torch.sqrt(num / den.clamp_min(torch.finfo(torch.float64).tiny)), torch.zeros_like(den))
+
+
+def griffinlim(mag, stft, n_iter=32, momentum=0.99, length=None, init_phase=None, rand_init=True, generator=None, frames=None,
+               return_convergence=False):
+    """a waveform whose STFT magnitude approaches `mag` (..., K, F), by the loop of include/psnd.h - torchaudio's functional.griffinlim,
+    librosa's griffinlim (fast Griffin-Lim, Perraudin et al. 2013) - with `stft.transform_complex` / `stft.inverse_complex` as the two
+    transforms (models.transforms.STFT): X0 from griffinlim_start, then `n_iter` times inverse, transform, griffinlim_step with
+    alpha = momentum / (1 + momentum) and eps = 1e-16, then the inverse.  Returns (..., length or (F - 1) hop) in mag's dtype and on its
+    device, trimmed or zero-padded; with `return_convergence` also conv (n_iter, N) float64, conv[i, n] = sqrt(sum (|C| - S)^2 / sum S^2)
+    of iteration i.  `init_phase` (mag's shape) sets the first phase; else `rand_init` draws 2 pi torch.rand(...) once on mag's device
+    (`generator`); else the phase is 0.  0 <= momentum < 1; n_iter >= 0, n_iter = 0 returns the inverse of X0.  `frames` as in
+    griffinlim_start.
+
+    On HIP tensors every iteration is three calls of the library and no library op: the two transforms and psnd_griffinlim_step, which
+    writes X over the buffers of the spectrum of the iteration before; nothing synchronises with the host, so the loop can be captured.
+    Off the iterated path and in library ops: the one draw of the random phase, and - with `return_convergence` - one float64 reduction
+    of the per-chunk sums after the last iteration.  CPU tensors run the same loop through the host transforms in float64 and are cast
+    back.  Runs under torch.no_grad(): no autograd, gradients through the loop are out of scope."""
+    who = 'griffinlim'
+    if not isinstance(mag, torch.Tensor):
+        raise _lib.PsndError('%s: a tensor is expected, got %s' % (who, type(mag).__name__))
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+        raise ValueError('%s: n_iter=%r - an integer >= 0' % (who, n_iter))
+    try:
+        m = float(momentum)
+    except (TypeError, ValueError):
+        raise ValueError('%s: momentum=%r - a number in [0, 1)' % (who, momentum))
+    if isinstance(momentum, bool) or not 0.0 <= m < 1.0:
+        raise ValueError('%s: momentum=%r - a number in [0, 1)' % (who, momentum))
+    if length is not None and (isinstance(length, bool) or not isinstance(length, int) or length < 0):
+        raise ValueError('%s: length=%r - an integer >= 0 or None' % (who, length))
+    lead, N, K, F, frames = _gl_planes(who, [('mag', mag), ('init_phase', init_phase)], frames)
+    if K != stft.filter_length // 2 + 1:
+        raise _lib.PsndError('%s: mag has %d bins, STFT(%d, %d) has %d' % (who, K, stft.filter_length, stft.hop_length, stft.filter_length // 2 + 1))
+    hop = stft.hop_length
+    if n_iter > 0 and (F - 1) * hop <= stft.filter_length // 2:
+        raise _lib.PsndError('%s: %d frames give %d samples, the transform\'s reflect padding needs more than %d' % (
+            who, F, max(F - 1, 0) * hop, stft.filter_length // 2))
+    alpha = m / (1.0 + m)
+    work = torch.float32 if mag.is_cuda else torch.float64
+    with torch.no_grad():
+        S = mag.detach().reshape(N, K, F).to(work).contiguous()
+        if init_phase is not None:
+            phi = init_phase.detach().reshape(N, K, F).to(work)
+        elif rand_init:
+            phi = ((2.0 * math.pi) * torch.rand((N, K, F), dtype=torch.float32, device=mag.device, generator=generator)).to(work)
+        else:
+            phi = None
+        X = griffinlim_start(S, phi, frames)
+        P, parts = None, []
+        for _ in range(n_iter):
+            C = stft.transform_complex(stft.inverse_complex(X[0], X[1]))
+            C = (C[0].to(work), C[1].to(work))
+            r = griffinlim_step(S, C[0], C[1], None if P is None else P[0], None if P is None else P[1], alpha, GL_EPS, frames,
+                                out=P if mag.is_cuda else None, partial=return_convergence)
+            X, P = r[:2], C
+            if return_convergence:
+                parts.append(r[2])
+        y = stft.inverse_complex(X[0], X[1])
+        n = (F - 1) * hop if length is None else length
+        if y.shape[-1] >= n:
+            y = y[..., :n].contiguous()
+        else:
+            y = torch.nn.functional.pad(y, (0, n - y.shape[-1]))
+        y = y.to(mag.dtype).reshape(lead + (n,))
+        if not return_convergence:
+            return y
+        conv = _gl_convergence(torch.stack(parts)) if parts else torch.zeros((0, N), dtype=torch.float64, device=mag.device)
+    return y, conv
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

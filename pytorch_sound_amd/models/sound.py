@@ -1,5 +1,5 @@
 """Drop-in for pytorch_sound/models/sound.py: VolNormConv, PreEmphasis, InversePreEmphasis, build_stft_functions,
-multi_stft_loss - same names, arguments and results - and Resample, TimeStretch and PitchShift, which the reference does not have.
+multi_stft_loss - same names, arguments and results - and Resample, TimeStretch, PitchShift and GriffinLim, which the reference does not have.
 
 On a HIP device every class here runs on libpsnd_hip.so (psnd_volnorm_*, psnd_preemphasis_*, psnd_ipreemph_*, psnd_stft_fwd/bwd,
 psnd_stft_loss_*); CPU tensors take the reference's torch formulation (host-side use: tests, data preparation).
@@ -221,6 +221,36 @@ class PitchShift(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return 'sr=%r, n_steps=%r, bins_per_octave=%r, p=%d, q=%d' % (self.sr, self.n_steps, self.bins_per_octave, self.p, self.q)
+
+
+class GriffinLim(torch.nn.Module):
+    """``kernels.griffinlim`` as a module on magnitudes (N, K, F) or (K, F) with K = n_fft // 2 + 1, no parameters: ``n_iter`` iterations
+    of fast Griffin-Lim (torchaudio's / librosa's definition, include/psnd.h), (F - 1) hop_length samples per item.  ``power``: the
+    exponent of the input (2 for a power spectrogram); ``S ** (1 / power)`` is taken first when it is not 1.  The module owns its STFT,
+    whose plan is cached per device: with ``rand_init=False`` (a zero first phase) a call after the first copies nothing from the host and
+    can be captured.  No gradient."""
+
+    def __init__(self, n_fft: int = 1024, hop_length: int = 256, n_iter: int = 32, momentum: float = 0.99, power: float = 1.0,
+                 rand_init: bool = True):
+        super().__init__()
+        from pytorch_sound_amd.models.transforms import STFT as ConvSTFT
+        if not float(power) > 0.0:
+            raise ValueError('GriffinLim: power=%r must be positive' % (power,))
+        if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0 or isinstance(momentum, bool) or not 0.0 <= float(momentum) < 1.0:
+            raise ValueError('GriffinLim: n_iter=%r momentum=%r - an integer >= 0, a number in [0, 1)' % (n_iter, momentum))
+        self.n_iter, self.momentum, self.power, self.rand_init = n_iter, float(momentum), float(power), bool(rand_init)
+        self.stft = ConvSTFT(n_fft, hop_length)
+
+    def forward(self, magnitude: torch.Tensor, length: int = None) -> torch.Tensor:
+        if magnitude.dim() not in (2, 3):
+            raise RuntimeError('GriffinLim expects a (N, K, F) or (K, F) tensor, got %s' % (tuple(magnitude.shape),))
+        if self.power != 1.0:
+            magnitude = magnitude.detach() ** (1.0 / self.power)
+        return K.griffinlim(magnitude, self.stft, self.n_iter, self.momentum, length, None, self.rand_init)
+
+    def extra_repr(self) -> str:
+        return 'n_fft=%d, hop_length=%d, n_iter=%d, momentum=%r, power=%r, rand_init=%r' % (
+            self.stft.filter_length, self.stft.hop_length, self.n_iter, self.momentum, self.power, self.rand_init)
 
 
 #

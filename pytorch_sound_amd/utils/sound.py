@@ -6,6 +6,7 @@
     resample                       sample-rate conversion (the reference shells out: scripts/preprocess.py:82-88 sox, :32-41 ffmpeg)
     time_stretch, pitch_shift      duration without pitch and pitch without duration (the reference reaches sox's `tempo` / `pitch` through
                                    pysndfx's AudioEffectsChain)
+    griffinlim                     a waveform from a magnitude spectrogram alone (the reference has none; it imports librosa throughout)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -34,6 +35,12 @@ shift is that stretch followed by `resample_poly` with the fraction `kernels.pit
 native (`STFT.transform_complex`, psnd_phase_vocoder.hip, `psnd_istft_reim`; the phase is summed as a fixed-point fraction of a turn, so
 a long clip keeps it); numpy arrays and CPU tensors run the same definition in float64 numpy between the host STFTs.  No transient or
 formant handling, no phase locking, no gradient.
+
+`griffinlim` is not something the reference has, so there is no parity to pin: it is torchaudio's `functional.griffinlim` / librosa's
+`griffinlim` (fast Griffin-Lim, Perraudin et al. 2013) by the definition written out in include/psnd.h, on this project's `STFT` - the
+reference's framing and inverse (`transform_complex`, `inverse_complex`), not torch.stft's.  On a HIP tensor every iteration is the two
+native transforms and one launch of psnd_griffinlim.hip between them; numpy arrays and CPU tensors run the same loop in float64 through
+the host transforms.  No early stopping, no gradient.
 """
 import math
 
@@ -192,6 +199,30 @@ def pitch_shift(wav, sr, n_steps, bins_per_octave=12, n_fft=1024, hop_length=256
     ratio = kernels.pitch_ratio(n_steps, bins_per_octave)
     stft = _stft(n_fft, hop_length)
     return _effect(lambda rows: shift_rows(rows, ratio, stft), wav, 'pitch_shift')
+
+
+def griffinlim(magnitude, n_iter=32, n_fft=None, hop_length=None, momentum=0.99, length=None, init_phase=None, rand_init=True):
+    """a waveform (..., length or (F - 1) hop_length) whose STFT magnitude approaches `magnitude` (..., K, F): `n_iter` iterations of fast
+    Griffin-Lim (torchaudio's / librosa's definition, include/psnd.h) with momentum in [0, 1) on STFT(n_fft, hop_length) of this project;
+    n_fft defaults to 2 (K - 1), hop_length to n_fft // 4.  `init_phase` (the magnitude's shape) sets the first phase, else `rand_init`
+    draws it uniformly once, else it is 0.  `kernels.griffinlim` does the work.  numpy in -> float32 numpy out; tensor in -> tensor of the
+    same dtype and device out (float64 on a HIP tensor raises).  No gradient."""
+    import torch
+    if not _is_tensor(magnitude):
+        m = np.asarray(magnitude)
+        if m.ndim < 2:
+            raise kernels.PsndError('griffinlim: the input needs a bin and a frame axis')
+        if init_phase is not None:
+            init_phase = torch.from_numpy(np.ascontiguousarray(init_phase, dtype=np.float32))
+        return griffinlim(torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)), n_iter, n_fft, hop_length, momentum, length, init_phase,
+                          rand_init).numpy()
+    if magnitude.dim() < 2:
+        raise kernels.PsndError('griffinlim: the input needs a bin and a frame axis')
+    if n_fft is None:
+        n_fft = 2 * (magnitude.shape[-2] - 1)
+    if hop_length is None:
+        hop_length = n_fft // 4
+    return kernels.griffinlim(magnitude, _stft(n_fft, hop_length), n_iter, momentum, length, init_phase, rand_init)
 
 
 def get_wav_duration(file):
