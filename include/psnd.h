@@ -849,6 +849,54 @@ int psnd_griffinlim_start(const float *mag, const float *phase, int64_t N, int64
 int psnd_griffinlim_step(const float *mag, const float *cre, const float *cim, const float *pre, const float *pim, int64_t N, int64_t K,
                          int64_t F, const int64_t *frames, float alpha, float eps, float *xre, float *xim, float *partial, void *stream);
 
+/* ---- mel to linear magnitude on device tensors (psnd_mel_inverse.hip): what kernels.mel_inverse, models.transforms.InverseMelScale,
+ *  LogMelSpectrogram.inverse_mel, utils.sound.mel_to_magnitude / mel_to_wave and models.sound.MelToWave are built on.  Every frame is an
+ *  independent non-negative least-squares problem, M equations in K unknowns, solved by a fixed number of FISTA steps (Beck and Teboulle
+ *  2009) from a flat-band guess.  torchaudio's InverseMelScale (lstsq) and librosa's mel_to_stft (NNLS by L-BFGS-B) are other algorithms:
+ *  the definition below is the contract, there is no parity to pin.
+ *  Inputs.   W : (M, K) fp32, finite and >= 0 (a negative or non-finite weight is PSND_E_ARG of the plan builder, not a clamp).
+ *            Y = mel : fp32 (N, M, F), the frame axis contiguous.  log_kind in {PSND_LOG_NONE, PSND_LOG_E, PSND_LOG_10}, log_offset.
+ *            n_iter >= 0.  frames : one int64 per item n (device), clamped to [0, F], or NULL for F_n = F everywhere.
+ *  The plan (host, float64; every sum below adds its terms one after the other in ascending index, products are not fused).
+ *      s[m] = sum_k W[m,k];  d[m] = 1 / s[m] if s[m] > 0 else 0 (an empty band drops out of the problem)
+ *      A = fp32(d[m] W[m,k]): rows that sum to 1 - the raw Slaney-normalised system is badly scaled from the low bands to the high ones.
+ *          Only A is rounded; everything below is formed from the ROUNDED A, in float64.
+ *      c[k] = sum_m A[m,k];  cinv[k] = 1 / c[k] if c[k] > 0 else 0
+ *      L = max_m sum_k A[m,k] c[k], the largest row sum of A A^T, a bound of its largest eigenvalue because A >= 0 (no eigen-solver:
+ *          the host code and numpy get it to the bit);  step = 1 / L, or 0 if L = 0
+ *      beta_i = (t_{i-1} - 1) / t_i,  t_0 = 1,  t_i = (1 + sqrt(1 + 4 t_{i-1}^2)) / 2,  i = 1 .. n_iter_max; in float64, stored as fp32
+ *      The kernel takes d, cinv and step rounded to fp32.
+ *  Each valid frame (m and k run over all filters and bins; the vectors are the frame's own).
+ *      lin[m] = Y (LOG_NONE), exp(Y) - log_offset (LOG_E), 10^Y - log_offset (LOG_10);   b[m] = d[m] max(lin[m], 0)
+ *      x_0[k] = cinv[k] sum_m A[m,k] b[m]   (the flat-band guess);   z = x_0
+ *      for i = 1 .. n_iter:   r = A z - b;   g = A^T r;   x_i = max(z - step g, 0);   z = x_i + beta_i (x_i - x_{i-1})
+ *      out = x_{n_iter}, (N, K, F).   resid (optional, (N, F)) = sqrt(sum_m r[m]^2 / sum_m b[m]^2) with r = A x_{n_iter} - b, 0 where b = 0.
+ *  What follows.  A bin no filter reaches (c[k] = 0) is exactly 0 at every iteration.  Frames f >= F_n are never read, whatever the
+ *  memory holds, and come out as 0 (out and resid).  Frames never interact: a non-finite value in a frame may make that frame's output
+ *  anything (max(NaN, 0) is 0 here), and leaves every other frame's bits as they are.
+ *  Freedoms of the implementation: fused or unfused multiply-adds, the device library's expf / exp10f / sqrtf.  The order of every sum
+ *  (ascending m or k over the band from the first to the last non-zero weight) is fixed: repeated launches agree bit for bit, and a
+ *  frame's bits depend on nothing but its own column of Y - not on f, n, N, F or its neighbours.
+ *  The plan, in 4-byte words: a header of 32 words {magic, M, K, n_iter_max, weights in the row bands, weights in the column bands,
+ *  step as fp32, 0, then the word offsets of d fp32[M], cinv fp32[K], beta fp32[psnd_mel_inverse_max_iter()], the row bands (per filter
+ *  {first bin | length << 16, offset into the row weights}), the column bands (per bin {first filter | length << 16, offset}), the row
+ *  weights, the column weights, A fp32 (M, K) dense, the float64 block {step, L, d[M], cinv[K]}, and the word count}.  One launch, a
+ *  workgroup owns psnd_mel_inverse_tile(M, K) consecutive frames of one item and keeps x, z, r and b in LDS for all iterations; no scratch,
+ *  no atomics, no host synchronisation.  psnd_mel_inverse_tile: the frames per workgroup, the one size the kernel's seams depend on (a
+ *  function, as psnd_gl_chunk, not a macro); 0 outside the sizes served.
+ *  PSND_E_UNSUPPORTED (psnd_last_error names the limit): M > 256, K > 2049, n_iter or n_iter_max > psnd_mel_inverse_max_iter();
+ *      psnd_mel_inverse_plan_bytes returns 0 there.  PSND_E_ARG: a null pointer with work to do, sizes <= 0, a bad log_kind, a bad weight.
+ *      PSND_E_SHAPE: K F >= 2^31 or more than 2^31 - 1 workgroups.  N F == 0: PSND_OK, nothing launched.  What the host cannot see (the
+ *      plan lives on the device) - memory that is no plan (the magic word), a plan built for another (M, K), n_iter above the n_iter_max
+ *      the plan was built with - is found by the launch itself from the first four words of the plan: it reads nothing else of it and
+ *      fills out and resid with NaN. */
+int psnd_mel_inverse_tile(int M, int K);
+int psnd_mel_inverse_max_iter(void);
+size_t psnd_mel_inverse_plan_bytes(int M, int K);
+int psnd_mel_inverse_plan_build(int M, int K, const float *mel_filter_host, int n_iter_max, void *plan_host);
+int psnd_mel_inverse(const float *mel, int64_t N, int64_t F, int M, int K, const void *plan, int log_kind, float log_offset, int n_iter,
+                     const int64_t *frames, float *out, float *resid, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

@@ -2,7 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder` and the `griffinlim*` functions alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder`, the `griffinlim*` functions and `mel_inverse` alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import math
@@ -1986,6 +1986,214 @@ def griffinlim(mag, stft, n_iter=32, momentum=0.99, length=None, init_phase=None
             return y
         conv = _gl_convergence(torch.stack(parts)) if parts else torch.zeros((0, N), dtype=torch.float64, device=mag.device)
     return y, conv
+
+
+MEL_INVERSE_ITER_MAX = 256      # the momentum factors a plan is built with unless told otherwise
+
+
+def mel_inverse_tile(M, K):
+    """psnd_mel_inverse_tile: the consecutive frames of one item a workgroup of psnd_mel_inverse.hip owns - the size its seams depend on"""
+    return int(lib().psnd_mel_inverse_tile(int(M), int(K)))
+
+
+def _mi_filter(mel_filter, who):
+    if isinstance(mel_filter, torch.Tensor):
+        mel_filter = mel_filter.detach().cpu().numpy()
+    W = np.array(mel_filter, dtype=np.float32, order='C')         # a copy: a plan is built lazily and must not follow later writes to the caller's array
+    if W.ndim != 2 or W.size == 0:
+        raise _lib.PsndError('%s: the filterbank must be a non-empty (M, K) matrix, got %s' % (who, W.shape))
+    if not np.isfinite(W).all() or (W < 0).any():
+        raise _lib.PsndError('%s: the filterbank must be finite and >= 0 (a negative or non-finite weight is an error, not a clamp)' % who)
+    return W
+
+
+def mel_inverse_plan_host(mel_filter, n_iter_max=MEL_INVERSE_ITER_MAX):
+    """the plan of include/psnd.h's mel-inverse section in numpy: {A fp32 (M, K), d, cinv, c float64, L, step floats, beta fp32
+    (n_iter_max,)}.  Every sum adds its terms one after the other in ascending index, as the C++ builder does: the two agree to the bit."""
+    W = _mi_filter(mel_filter, 'mel_inverse_plan').astype(np.float64)
+    M, K = W.shape
+    s = np.zeros(M)
+    for k in range(K):
+        s = s + W[:, k]
+    d = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)
+    A = (d[:, None] * W).astype(np.float32)
+    A64 = A.astype(np.float64)
+    c = np.zeros(K)
+    for m in range(M):
+        c = c + A64[m]
+    cinv = np.where(c > 0, 1.0 / np.where(c > 0, c, 1.0), 0.0)
+    rows = np.zeros(M)
+    for k in range(K):
+        rows = rows + A64[:, k] * c[k]
+    L = float(rows.max())
+    beta, t = np.zeros(int(n_iter_max), dtype=np.float32), 1.0
+    for i in range(int(n_iter_max)):
+        tn = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
+        beta[i] = (t - 1.0) / tn
+        t = tn
+    return dict(A=A, d=d, cinv=cinv, c=c, L=L, step=1.0 / L if L > 0 else 0.0, beta=beta)
+
+
+class MelInversePlan:
+    """what mel_inverse needs of a filterbank (M, K): the numpy plan (A, d, cinv, step, beta: mel_inverse_plan_host) for CPU tensors and,
+    built on first use through psnd_mel_inverse_plan_build and then kept per device, the table the kernel reads.  `raw()` is the C-built
+    plan as a dict of views (the same names, plus d32, cinv32, step32 - what the kernel takes - and the band tables)."""
+
+    def __init__(self, mel_filter, n_iter_max=MEL_INVERSE_ITER_MAX):
+        if isinstance(n_iter_max, bool) or not isinstance(n_iter_max, int) or n_iter_max < 0:
+            raise ValueError('mel_inverse_plan: n_iter_max=%r - an integer >= 0' % (n_iter_max,))
+        self.W = _mi_filter(mel_filter, 'mel_inverse_plan')
+        self.W.setflags(write=False)
+        self.M, self.K = self.W.shape
+        self.n_iter_max = n_iter_max
+        self._np = None
+        self._host = None
+        self._dev = {}
+
+    @property
+    def host(self):
+        if self._np is None:
+            self._np = mel_inverse_plan_host(self.W, self.n_iter_max)
+        return self._np
+
+    def bytes(self):
+        """the plan psnd_mel_inverse_plan_build writes, a numpy uint8 array (host)"""
+        if self._host is None:
+            nb = int(lib().psnd_mel_inverse_plan_bytes(self.M, self.K))
+            if nb == 0:
+                raise _lib.PsndError('mel_inverse_plan: M=%d K=%d: psnd_mel_inverse serves M <= 256 filters and K <= 2049 bins' % (self.M, self.K))
+            plan = np.zeros(nb, dtype=np.uint8)
+            check(lib().psnd_mel_inverse_plan_build(self.M, self.K, _lib.np_ptr(self.W), self.n_iter_max, _lib.np_ptr(plan)),
+                  'psnd_mel_inverse_plan_build')
+            self._host = plan
+        return self._host
+
+    def raw(self):
+        w = self.bytes().view(np.uint32)
+        M, K = int(w[1]), int(w[2])
+        f64 = w[int(w[16]):int(w[16]) + 2 * (2 + M + K)].view(np.float64)
+        f32 = lambda off, n: w[int(off):int(off) + n].view(np.float32)      # noqa: E731
+        return dict(M=M, K=K, n_iter_max=int(w[3]), nnz_rows=int(w[4]), nnz_cols=int(w[5]), step32=float(w[6:7].view(np.float32)[0]),
+                    d32=f32(w[8], M), cinv32=f32(w[9], K), beta=f32(w[10], int(w[3])), row_bands=w[int(w[11]):int(w[11]) + 2 * M].reshape(M, 2),
+                    col_bands=w[int(w[12]):int(w[12]) + 2 * K].reshape(K, 2), row_weights=f32(w[13], int(w[4])), col_weights=f32(w[14], int(w[5])),
+                    A=f32(w[15], M * K).reshape(M, K), step=float(f64[0]), L=float(f64[1]), d=f64[2:2 + M], cinv=f64[2 + M:2 + M + K])
+
+    def tensor(self, device):
+        """the plan on `device`; copied from the host once per device"""
+        key = str(torch.device(device))
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = plan_tensor(self.bytes()).to(device)
+        return t
+
+    def to(self, device):
+        if torch.device(device).type == 'cuda':
+            self.tensor(device)
+        return self
+
+
+def mel_inverse_plan(mel_filter, n_iter_max=MEL_INVERSE_ITER_MAX):
+    """MelInversePlan of a filterbank (M, K), finite and >= 0 (PsndError otherwise), good for up to n_iter_max iterations"""
+    return MelInversePlan(mel_filter, n_iter_max)
+
+
+def _mi_plan(plan_or_filter, n_iter):
+    if isinstance(plan_or_filter, MelInversePlan):
+        return plan_or_filter
+    return MelInversePlan(plan_or_filter, max(int(n_iter), 0))
+
+
+def _mi_undo_log(Y, log_kind, log_offset):
+    if log_kind == LOG_E:
+        return np.exp(Y) - log_offset
+    if log_kind == LOG_10:
+        return np.power(10.0, Y) - log_offset
+    if log_kind == LOG_NONE:
+        return Y
+    raise ValueError('mel_inverse: log_kind=%r' % (log_kind,))
+
+
+def mel_inverse_host(mel, plan_or_filter, n_iter=64, log_kind=LOG_NONE, log_offset=0.0, frames=None, return_residual=False):
+    """the mel-inverse section of include/psnd.h on a float64 numpy array (N, M, F): the definition, all frames at once - and the CPU
+    path of mel_inverse.  Returns x (N, K, F) float64, with `return_residual` also |A x - b| / |b| per frame (N, F)."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError('mel_inverse: n_iter=%r - an integer >= 0' % (n_iter,))
+    plan = _mi_plan(plan_or_filter, n_iter)
+    Y = np.asarray(mel, dtype=np.float64)
+    if Y.ndim != 3 or Y.shape[1] != plan.M:
+        raise ValueError('mel_inverse: (N, %d, F) expected, got %s' % (plan.M, Y.shape))
+    if n_iter > plan.n_iter_max:
+        raise ValueError('mel_inverse: n_iter=%d, the plan was built for %d' % (n_iter, plan.n_iter_max))
+    N, _, F = Y.shape
+    h = plan.host
+    A, d, cinv, step, beta = h['A'].astype(np.float64), h['d'], h['cinv'], h['step'], h['beta']
+    live = np.arange(F)[None, None, :] < _gl_host_frames(frames, N, F)[:, None, None]
+    with np.errstate(invalid='ignore', over='ignore'):
+        lin = _mi_undo_log(np.where(live, Y, 0.0), log_kind, float(log_offset))
+        b = np.where(live, d[None, :, None] * np.maximum(lin, 0.0), 0.0)
+        x = cinv[None, :, None] * np.einsum('mk,nmf->nkf', A, b)
+        z = x
+        for i in range(n_iter):
+            r = np.einsum('mk,nkf->nmf', A, z) - b
+            g = np.einsum('mk,nmf->nkf', A, r)
+            xn = np.maximum(z - step * g, 0.0)
+            z = xn + float(beta[i]) * (xn - x)
+            x = xn
+        x = np.where(live, x, 0.0)
+        if not return_residual:
+            return x
+        r = np.einsum('mk,nkf->nmf', A, x) - b
+        rr, bb = (r * r).sum(axis=1), (b * b).sum(axis=1)
+        return x, np.where(bb > 0, np.sqrt(rr / np.where(bb > 0, bb, 1.0)), 0.0)
+
+
+def mel_inverse(mel, plan_or_filter, n_iter=64, log_kind=LOG_NONE, log_offset=0.0, frames=None, return_residual=False):
+    """a linear magnitude (..., K, F) >= 0 whose mel projection approaches `mel` (..., M, F), by the definition of include/psnd.h: per
+    frame min_{x >= 0} |A x - b|^2 with the row-normalised filterbank A, `n_iter` FISTA steps from the flat-band guess (n_iter = 0 returns
+    the guess).  `plan_or_filter`: a MelInversePlan (mel_inverse_plan - keeps the device table, nothing is copied from the host after its
+    first use on a device) or the (M, K) filterbank itself, finite and >= 0 (a plan is then built in the call).  `log_kind`, `log_offset`:
+    what `mel` is - linear (LOG_NONE), log(lin + offset) (LOG_E) or log10(lin + offset) (LOG_10).  `frames`: valid frames per item (one
+    integer per leading index, clamped to [0, F]); what lies behind is never read and comes out 0.  `return_residual`: also
+    |A x - b| / |b| per frame, (..., F), float32 on HIP tensors and float64 on CPU tensors.
+
+    HIP tensors run psnd_mel_inverse (float32; float16 / bfloat16 are cast in and out; float64 raises; non-contiguous input is made
+    contiguous): ONE launch for all iterations, no library op, no host synchronisation - the call can be captured.  CPU tensors go through
+    mel_inverse_host in float64.  The result is in mel's dtype and on its device.  No autograd."""
+    who = 'mel_inverse'
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+        raise ValueError('%s: n_iter=%r - an integer >= 0' % (who, n_iter))
+    if log_kind not in (LOG_NONE, LOG_E, LOG_10):
+        raise ValueError('%s: log_kind=%r' % (who, log_kind))
+    plan = _mi_plan(plan_or_filter, n_iter)
+    lead, N, M, F, frames = _gl_planes(who, [('mel', mel)], frames)
+    if M != plan.M:
+        raise _lib.PsndError('%s: mel has %d bands, the filterbank %d' % (who, M, plan.M))
+    if n_iter > plan.n_iter_max:
+        raise _lib.PsndError('%s: n_iter=%d, the plan was built for %d (mel_inverse_plan(mel_filter, n_iter_max))' % (who, n_iter, plan.n_iter_max))
+    Kb = plan.K
+    if not mel.is_cuda:
+        r = mel_inverse_host(mel.detach().reshape(N, M, F).to(torch.float64).numpy(), plan, n_iter, log_kind, log_offset,
+                             None if frames is None else frames.numpy(), return_residual)
+        x = torch.from_numpy(np.ascontiguousarray(r[0] if return_residual else r)).to(mel.dtype).reshape(lead + (Kb, F))
+        return (x, torch.from_numpy(np.ascontiguousarray(r[1])).reshape(lead + (F,))) if return_residual else x
+    Y = mel.detach().reshape(N, M, F).float().contiguous()
+    out = torch.empty((N, Kb, F), dtype=torch.float32, device=mel.device)
+    resid = torch.empty((N, F), dtype=torch.float32, device=mel.device) if return_residual else None
+    if N * F > 0:
+        table = plan.tensor(mel.device)
+        with on(mel.device) as hip:
+            hip.psnd_mel_inverse(Y, N, F, M, Kb, table, int(log_kind), float(log_offset), n_iter, frames, out, resid)
+    x = out.to(mel.dtype).reshape(lead + (Kb, F))
+    return (x, resid.reshape(lead + (F,))) if return_residual else x
+
+
+def mel_to_wave(mel, plan_or_filter, stft, n_iter=64, gl_iter=32, momentum=0.99, log_kind=LOG_NONE, log_offset=0.0, length=None,
+                rand_init=True, generator=None, frames=None):
+    """mel (..., M, F) -> waveform (..., length or (F - 1) hop): mel_inverse (`n_iter` steps, one launch), then griffinlim (`gl_iter`
+    iterations, `momentum`) on `stft` - two calls on device tensors, no library op on either iterated path, capturable with
+    rand_init=False.  No autograd."""
+    mag = mel_inverse(mel, plan_or_filter, n_iter, log_kind, log_offset, frames)
+    return griffinlim(mag, stft, gl_iter, momentum, length, None, rand_init, generator, frames)
 
 
 def volnorm_forward(wav, window, hop, inv_gain, out_len):

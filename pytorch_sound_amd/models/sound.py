@@ -1,5 +1,6 @@
 """Drop-in for pytorch_sound/models/sound.py: VolNormConv, PreEmphasis, InversePreEmphasis, build_stft_functions,
-multi_stft_loss - same names, arguments and results - and Resample, TimeStretch, PitchShift and GriffinLim, which the reference does not have.
+multi_stft_loss - same names, arguments and results - and Resample, TimeStretch, PitchShift, GriffinLim and MelToWave, which the reference
+does not have.
 
 On a HIP device every class here runs on libpsnd_hip.so (psnd_volnorm_*, psnd_preemphasis_*, psnd_ipreemph_*, psnd_stft_fwd/bwd,
 psnd_stft_loss_*); CPU tensors take the reference's torch formulation (host-side use: tests, data preparation).
@@ -251,6 +252,27 @@ class GriffinLim(torch.nn.Module):
     def extra_repr(self) -> str:
         return 'n_fft=%d, hop_length=%d, n_iter=%d, momentum=%r, power=%r, rand_init=%r' % (
             self.stft.filter_length, self.stft.hop_length, self.n_iter, self.momentum, self.power, self.rand_init)
+
+
+class MelToWave(torch.nn.Module):
+    """``utils.sound.mel_to_wave`` as a module on mels (N, mel_size, F) or (mel_size, F), no parameters: ``InverseMelScale`` (``n_iter``
+    FISTA steps per frame, include/psnd.h) followed by ``GriffinLim`` (``gl_iter`` iterations) - a waveform of (F - 1) hop_length samples
+    from a mel spectrogram alone, without a vocoder checkpoint.  ``log``: None for a linear mel, 'e' / '10' for a logarithm of
+    mel + log_offset.  The module owns its filterbank plan and its STFT, both cached per device: with ``rand_init=False`` a call after
+    the first copies nothing from the host and can be captured.  No gradient."""
+
+    def __init__(self, sample_rate: int, mel_size: int, n_fft: int = 1024, hop_length: int = 256, mel_min: float = 0., mel_max: float = None,
+                 n_iter: int = 64, gl_iter: int = 32, momentum: float = 0.99, log: str = None, log_offset: float = 1e-6,
+                 rand_init: bool = True):
+        super().__init__()
+        from pytorch_sound_amd.models.transforms import InverseMelScale
+        self.inverse_mel = InverseMelScale(sample_rate, mel_size, n_fft, mel_min, mel_max, n_iter, log, log_offset)
+        self.griffinlim = GriffinLim(n_fft, hop_length, gl_iter, momentum, 1.0, rand_init)
+
+    def forward(self, mel: torch.Tensor, length: int = None) -> torch.Tensor:
+        if mel.dim() not in (2, 3):
+            raise RuntimeError('MelToWave expects a (N, M, F) or (M, F) tensor, got %s' % (tuple(mel.shape),))
+        return self.griffinlim(self.inverse_mel(mel), length)
 
 
 #

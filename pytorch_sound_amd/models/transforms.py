@@ -9,6 +9,8 @@ LogMelSpectrogram    LogMelSpectrogram.forward              psnd_stft_fwd + psnd
 STFTTorchAudio       forward -> (re, im); transform         psnd_stft_fwd(re,im) / psnd_stft_bwd
 Audio2Mel            forward (N,1,T) -> log10 mel           psnd_stft_fwd(HIFIGAN) + psnd_mel_fwd
 LearnableSTFT        transform / inverse (HIP tensors)      psnd_lstft_analysis / _synthesis / _basis_grad
+LogMelScale          LogMelScale.forward (magnitude -> mel) psnd_mel_fwd (+ bwd)
+(none)               InverseMelScale, .inverse_mel          psnd_mel_inverse
 """
 from typing import Optional, Tuple
 
@@ -242,6 +244,83 @@ class LogMelSpectrogram(nn.Module):
                                % (self.mel_filter.shape[1], mag.shape[1]))
         return K.MelLog.apply(mag, self._mel_plan(), self.mel_size, K.LOG_E, float(log_offset), None,
                               self.min_db if self.min_db else None, self.max_db if self.max_db else None)
+
+    def inverse_mel(self, mel: torch.Tensor, log_offset: float = 1e-6, n_iter: int = 64) -> torch.Tensor:
+        """the way back from this module's output (..., mel_size, F) to a linear magnitude (..., n_fft // 2 + 1, F) >= 0:
+        ``kernels.mel_inverse`` with this module's ``mel_filter`` on exp(mel) - log_offset.  Not in the reference.  Where a clamp of
+        ``forward`` was active the clamped value is what gets inverted.  The plan is cached per device; no gradient."""
+        mf = self.mel_filter
+        key = ('mel_inverse', mf._version, mf.data_ptr(), tuple(mf.shape), max(n_iter, K.MEL_INVERSE_ITER_MAX))
+        plan = self._plans.get(key, mel.device, lambda: K.mel_inverse_plan(mf, key[-1]))
+        return K.mel_inverse(mel, plan, n_iter, K.LOG_E, float(log_offset))
+
+
+class LogMelScale(nn.Module):
+    """The reference's ``LogMelScale`` (transforms.py:247-268) as it is evidently meant: the mel projection of a MAGNITUDE
+    (N, n_fft // 2 + 1, F) or (n_fft // 2 + 1, F), then ln(mel + log_offset), clamped to [ln 10^(min_db/10), ln 10^(max_db/10)].  The
+    reference's constructor raises as written (it passes ``dtype`` to ``torch.Tensor(...)``, which takes none); what is built here is
+    the float32 ``mel_filter`` buffer that call was after.  Both clamps are always active, as in the reference's ``forward``.  HIP tensors
+    run ``psnd_mel_fwd`` / ``psnd_mel_bwd`` (``kernels.MelLog``, differentiable in the magnitude), CPU tensors ``host.mel_log``."""
+
+    def __init__(self, sample_rate: int, mel_size: int, n_fft: int, min_db: float, max_db: float, mel_min: float = 0.,
+                 mel_max: float = None):
+        super().__init__()
+        self.mel_size = mel_size
+        self.min_db = float(np.log(np.power(10, min_db / 10)))
+        self.max_db = float(np.log(np.power(10, max_db / 10)))
+        if not self.min_db <= self.max_db:
+            raise ValueError('LogMelScale: min_db=%r must not exceed max_db=%r' % (min_db, max_db))
+        self.register_buffer('mel_filter', torch.from_numpy(mel_filterbank(sample_rate, n_fft, mel_size, fmin=mel_min, fmax=mel_max)))
+        self._plans = _PlanCache()
+
+    def _mel_plan(self):
+        mf = self.mel_filter
+        key = ('mel', mf._version, mf.data_ptr(), tuple(mf.shape))
+        return self._plans.get(key, mf.device, lambda: K.mel_plan(mf.detach().cpu().numpy()))
+
+    def forward(self, magnitude: torch.Tensor, log_offset: float = 1e-6) -> torch.Tensor:
+        if magnitude.dim() not in (2, 3) or magnitude.shape[-2] != self.mel_filter.shape[1]:
+            raise RuntimeError('LogMelScale expects a (N, %d, F) or (%d, F) magnitude, got %s'
+                               % (self.mel_filter.shape[1], self.mel_filter.shape[1], tuple(magnitude.shape)))
+        if not magnitude.is_cuda:
+            return H.mel_log(magnitude, self.mel_filter, H.LOG_E, float(log_offset), None, self.min_db, self.max_db)
+        mag = magnitude if magnitude.dim() == 3 else magnitude[None]
+        out = K.MelLog.apply(mag, self._mel_plan(), self.mel_size, K.LOG_E, float(log_offset), None, self.min_db, self.max_db)
+        return out if magnitude.dim() == 3 else out[0]
+
+
+class InverseMelScale(nn.Module):
+    """mel spectrogram (..., mel_size, F) -> linear magnitude (..., n_fft // 2 + 1, F) >= 0, the way back from ``LogMelSpectrogram`` /
+    ``LogMelScale`` (same ``mel_filter``, from the same ``mel_filterbank`` call): ``kernels.mel_inverse``, per frame ``n_iter`` FISTA steps
+    on the non-negative least-squares problem of the row-normalised filterbank, by the definition of include/psnd.h.  Not in the reference;
+    torchaudio's module of this name solves another problem (``lstsq``) - parity unpinned.  ``log``: None for a linear mel, 'e' for
+    ln(mel + log_offset), '10' for log10(mel + log_offset).  The plan is cached per device: a call after the first copies nothing from
+    the host and can be captured.  One launch on a HIP tensor; float64 numpy on a CPU tensor.  No gradient."""
+
+    def __init__(self, sample_rate: int, mel_size: int, n_fft: int, mel_min: float = 0., mel_max: float = None, n_iter: int = 64,
+                 log: str = None, log_offset: float = 1e-6):
+        super().__init__()
+        if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+            raise ValueError('InverseMelScale: n_iter=%r - an integer >= 0' % (n_iter,))
+        from pytorch_sound_amd.utils.sound import _log_kind
+        self.log_kind = _log_kind(log)
+        self.log, self.log_offset = log, float(log_offset) if self.log_kind != K.LOG_NONE else 0.0
+        self.mel_size, self.n_fft, self.n_iter = mel_size, n_fft, n_iter
+        self.register_buffer('mel_filter', torch.from_numpy(mel_filterbank(sample_rate, n_fft, mel_size, fmin=mel_min, fmax=mel_max)))
+        self._plans = _PlanCache()
+
+    def _plan(self, device):
+        mf = self.mel_filter
+        key = ('mel_inverse', mf._version, mf.data_ptr(), tuple(mf.shape), max(self.n_iter, K.MEL_INVERSE_ITER_MAX))
+        return self._plans.get(key, device, lambda: K.mel_inverse_plan(mf, key[-1]))
+
+    def forward(self, mel: torch.Tensor, frames: torch.Tensor = None, return_residual: bool = False) -> torch.Tensor:
+        if mel.dim() < 2 or mel.shape[-2] != self.mel_size:
+            raise RuntimeError('InverseMelScale expects a (..., %d, F) mel, got %s' % (self.mel_size, tuple(mel.shape)))
+        return K.mel_inverse(mel, self._plan(mel.device), self.n_iter, self.log_kind, self.log_offset, frames, return_residual)
+
+    def extra_repr(self) -> str:
+        return 'mel_size=%d, n_fft=%d, n_iter=%d, log=%r, log_offset=%r' % (self.mel_size, self.n_fft, self.n_iter, self.log, self.log_offset)
 
 
 class STFTTorchAudio(nn.Module):

@@ -7,6 +7,7 @@
     time_stretch, pitch_shift      duration without pitch and pitch without duration (the reference reaches sox's `tempo` / `pitch` through
                                    pysndfx's AudioEffectsChain)
     griffinlim                     a waveform from a magnitude spectrogram alone (the reference has none; it imports librosa throughout)
+    mel_to_magnitude, mel_to_wave  a linear magnitude, and a waveform, from a mel spectrogram alone (the reference has none)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -41,6 +42,11 @@ formant handling, no phase locking, no gradient.
 reference's framing and inverse (`transform_complex`, `inverse_complex`), not torch.stft's.  On a HIP tensor every iteration is the two
 native transforms and one launch of psnd_griffinlim.hip between them; numpy arrays and CPU tensors run the same loop in float64 through
 the host transforms.  No early stopping, no gradient.
+
+`mel_to_magnitude` is the mel-inverse section of include/psnd.h: per frame the non-negative least-squares problem of the row-normalised
+filterbank, a fixed number of FISTA steps from a flat-band guess - one launch of psnd_mel_inverse.hip on a HIP tensor, float64 numpy on
+numpy arrays and CPU tensors.  torchaudio's `InverseMelScale` and librosa's `mel_to_stft` are other algorithms: parity unpinned.
+`mel_to_wave` is `mel_to_magnitude` followed by `griffinlim`.  No gradient.
 """
 import math
 
@@ -223,6 +229,53 @@ def griffinlim(magnitude, n_iter=32, n_fft=None, hop_length=None, momentum=0.99,
     if hop_length is None:
         hop_length = n_fft // 4
     return kernels.griffinlim(magnitude, _stft(n_fft, hop_length), n_iter, momentum, length, init_phase, rand_init)
+
+
+_LOG_KINDS = {None: kernels.LOG_NONE, 'e': kernels.LOG_E, 'ln': kernels.LOG_E, 'log': kernels.LOG_E, '10': kernels.LOG_10,
+              'log10': kernels.LOG_10}
+
+
+def _log_kind(log):
+    try:
+        return _LOG_KINDS[log]
+    except (KeyError, TypeError):
+        raise ValueError("log=%r - None (a linear mel), 'e' or '10'" % (log,))
+
+
+def _mel_plan(mel_filter, n_iter):
+    """a `kernels.MelInversePlan` as it is, a filterbank as a plan built for this call (nothing is cached on a tensor's address: a caller
+    with many calls builds the plan once with `kernels.mel_inverse_plan` and passes it, or uses `InverseMelScale` / `MelToWave`)"""
+    if isinstance(mel_filter, kernels.MelInversePlan):
+        return mel_filter
+    return kernels.mel_inverse_plan(mel_filter, max(n_iter, kernels.MEL_INVERSE_ITER_MAX))
+
+
+def mel_to_magnitude(mel, mel_filter, n_iter=64, log=None, log_offset=1e-6, frames=None, return_residual=False):
+    """a linear magnitude (..., K, F) >= 0 whose projection by `mel_filter` (M, K), finite and >= 0, approaches the mel spectrogram `mel`
+    (..., M, F): `kernels.mel_inverse`, `n_iter` FISTA steps per frame by the definition of include/psnd.h.  `log`: None for a linear mel,
+    'e' for log(lin + log_offset) (what LogMelSpectrogram gives), '10' for log10(lin + log_offset); `log_offset` is ignored for a linear
+    mel.  `mel_filter` may be a `kernels.MelInversePlan` (`kernels.mel_inverse_plan(mel_filter)`): the filterbank itself costs a plan
+    built on the host and copied to the device in every call, the plan nothing after its first use.  numpy in -> float32 numpy out; tensor in -> tensor of the same dtype and device
+    out (float64 on a HIP tensor raises).  No gradient."""
+    import torch
+    kind = _log_kind(log)
+    off = float(log_offset) if kind != kernels.LOG_NONE else 0.0
+    if not _is_tensor(mel):
+        m = np.ascontiguousarray(np.asarray(mel), dtype=np.float32)
+        r = mel_to_magnitude(torch.from_numpy(m), mel_filter, n_iter, log, log_offset, frames, return_residual)
+        return (r[0].numpy(), r[1].numpy().astype(np.float32)) if return_residual else r.numpy()
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+        raise ValueError('mel_to_magnitude: n_iter=%r - an integer >= 0' % (n_iter,))
+    return kernels.mel_inverse(mel, _mel_plan(mel_filter, n_iter), n_iter, kind, off, frames, return_residual)
+
+
+def mel_to_wave(mel, mel_filter, n_fft=None, hop_length=None, n_iter=64, gl_iter=32, momentum=0.99, log=None, log_offset=1e-6, length=None,
+                rand_init=True):
+    """a waveform (..., length or (F - 1) hop_length) from a mel spectrogram (..., M, F) alone: `mel_to_magnitude` (`n_iter` steps), then
+    `griffinlim` (`gl_iter` iterations, `momentum`) on STFT(n_fft, hop_length) of this project; n_fft defaults to 2 (K - 1), hop_length to
+    n_fft // 4.  Two calls of the library's loops on a HIP tensor, nothing leaves the device.  No gradient."""
+    mag = mel_to_magnitude(mel, mel_filter, n_iter, log, log_offset)
+    return griffinlim(mag, gl_iter, n_fft, hop_length, momentum, length, None, rand_init)
 
 
 def get_wav_duration(file):
