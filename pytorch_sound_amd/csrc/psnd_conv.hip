@@ -607,6 +607,7 @@ struct WgradParams {
     float g2_slope;
     // up_u > 0: the `xa` operand is the high-resolution view of a transposed conv (ConvParams, up_role 2): Ca = up_u * up_Cr
     int up_u, up_p, up_Lp, up_HP, up_LpO, up_HPO, up_Cr;
+    int stage;                    // lab builds (PSND_WGRAD_STAGE): 1 = `regs`, 2 = `dma` - the chunk loop of the plain body; 0 = the launch's own
 #ifdef PSND_TRACE
     long long *trace;
 #endif
@@ -822,9 +823,41 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t *p0) {   // rows r .. r+3
 // activation tile holds 32 + the span of all 12 taps (<= WXRN = 96 rows, three pieces per thread).
 constexpr int WXRN = 96;
 constexpr int kWgradNarrowLdsBytes = 2 * (32 + WXRN) * WTP * (int)sizeof(bf16_t);
+// DMA (a form of the plain body: no combine, not NARROW, WK == WKT, no g_out, no transposed-conv view; which launches take it:
+// conv_wgrad_plain below): the chunks reach LDS by LDS-DMA
+// (`buffer_load_dwordx4 ... lds`) instead of through registers, into a ring of WNS slots, WNS - 1 chunks ahead.  The register ring
+// above is WD = 2 chunks deep and cannot grow (WD = 3 / 4: 171 / 188 VGPRs, one workgroup per CU fewer); the DMA ring costs LDS only, and
+// the three ds_write_b128 per thread and chunk go away.  A wave instruction writes 64 lanes x 16 B = 1 KiB lane-linear from its M0 base,
+// i.e. wave w fills rows 8 w .. 8 w + 7 of a 32-row group at a 128-byte row pitch (thread (rr, cg) -> row rr, piece cg, as above).  At that
+// pitch rows r and r + 2 of a transposing read share their banks, so the image is swizzled on the SOURCE side: LDS piece c of tile row r
+// holds the row's piece c ^ wdma_f(r) - the four rows of a read then sit on four disjoint 16-bank groups, as with the 192-byte pitch.
+// Rows and channel pieces out of range take the out-of-range buffer offset: the range check makes the transfer write zeros.
+// Every chunk is three transfers per wave (g, x rows 0 .. 31, x rows 32 .. 63), in range or not, so the wait in front of chunk ch is the
+// constant vmcnt(3 (WNS - 2)); a raw s_barrier follows it (__syncthreads() would wait vmcnt(0) and drain the ring), behind the barrier the
+// slot of chunk ch - 1 is free and takes chunk ch + WNS - 1.  Same chunks, same kk, same taps per accumulator as above: the same bits.
+#ifndef PSND_WNS
+#define PSND_WNS 4
+#endif
+constexpr int WNS = PSND_WNS;                // ring slots (WNS x 12 KB: 48 KB, three workgroups per CU)
+constexpr int WDP = 64;                      // LDS row pitch of the DMA image (bf16): one 128-byte row of the 64-channel tile
+constexpr int kWgradDmaSlot = (32 + WXR) * WDP;                                    // bf16 per slot: the g tile, then the x tile
+constexpr int kWgradDmaLdsBytes = WNS * kWgradDmaSlot * (int)sizeof(bf16_t);
+static_assert(WNS >= 3 && 3 * (WNS - 2) <= 63 && kWgradDmaLdsBytes < 64 * 1024, "vmcnt is a 6-bit counter; M0 carries a 16-bit LDS offset");
+constexpr int kWgradMultiLdsBytes = kWgradDmaLdsBytes > kWgradLdsBytes ? kWgradDmaLdsBytes : kWgradLdsBytes;   // the batched launch
+#ifdef PSND_LAB
+constexpr int kWgradLaunchLdsBytes = kWgradMultiLdsBytes;     // every launch can be switched to the ring
+#else
+constexpr int kWgradLaunchLdsBytes = kWgradLdsBytes;          // the launches that keep the register-staged loop
+#endif
+__device__ __forceinline__ int wdma_f(int r) { return 4 * ((r >> 1) & 1); }        // piece swizzle of tile row r (f(r) = f(r + 4k))
+__device__ __forceinline__ bf16x8 tr_frag_dma(const bf16_t *p0) {
+    const v4s_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_t __attribute__((address_space(3))) *)(p0));
+    const v4s_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_t __attribute__((address_space(3))) *)(p0 + 4 * WDP));
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 // WK: taps per (wave of a) workgroup - 3, or 4 / 6 for the 7- / 11-tap layers of the paired backward (half the tap groups: the rows
 // are staged half as often and a split count of twice the size fits the same number of workgroups)
-template <bool COMB, bool NARROW = false, int WK = WKT>
+template <bool COMB, bool NARROW = false, int WK = WKT, bool DMA = false>
 __device__ __forceinline__ void conv_wgrad_body(const WgradParams &p, const int bx, const int by, const int bz, bf16_t *sT, const size_t tblk) {
 #if !PSND_WGRAD_TR
     conv_wgrad_body_v1(p, bx, by, bz, sT, tblk);
@@ -928,6 +961,88 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradParams &p, const int 
     };
     // this lane's piece of a transposing read: row (lane & 15) >> 2 of the 4-row block, channels 16 ((lane >> 4) & 1) + 4 (lane & 3) ..
     const int trow = 8 * kg + ((lane & 15) >> 2), tcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+    if constexpr (DMA) {
+        static_assert(!COMB && !NARROW && WK == WKT, "the LDS-DMA ring feeds the plain body only");
+        typedef __attribute__((address_space(3))) char *lds_ptr;
+        const unsigned ring = __builtin_amdgcn_readfirstlane((unsigned)(size_t)((lds_ptr)sT));       // LDS byte address of the ring (SGPR)
+        const unsigned wbase = ring + 1024u * __builtin_amdgcn_readfirstlane((unsigned)wave);          // + this wave's 8 rows of a 32-row group
+        auto dma_rsrc = [](const void *ptr, unsigned bytes) __attribute__((always_inline)) {
+            const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
+            u32x4 d;
+            d.x = __builtin_amdgcn_readfirstlane((unsigned)a);
+            d.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32)) & 0xffffu;
+            d.z = __builtin_amdgcn_readfirstlane(bytes);
+            d.w = 0x00020000u;
+            return d;
+        };
+        const u32x4 dG = dma_rsrc(p.G1, (unsigned)g_bytes), dX = dma_rsrc(p.xa, (unsigned)x_bytes);
+        // the piece this lane FETCHES for LDS piece cg of tile rows rr and rr + 32 (the same swizzle term), and its channel bounds
+        const int cs = cg ^ wdma_f(rr);
+        const bool gokd = co0 + 8 * cs < p.Cb, xokd = ci0 + 8 * cs < p.Ca;
+        auto issue = [&](int ch, unsigned slot) __attribute__((always_inline)) {
+            const long long r0 = rs + 32ll * ch, r = r0 + rr;
+            const unsigned og = (r < re && gokd) ? (unsigned)(((size_t)r * p.Cb + co0 + 8 * cs) * sizeof(bf16_t)) : OOB;
+            unsigned ox[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int xi = rr + 32 * u;
+                const long long rx = r0 + lo + xi;
+                const bool ok = xi < xrows && rx >= 0 && rx < p.R && xokd;
+                ox[u] = ok ? (unsigned)(((size_t)rx * p.Ca + ci0 + 8 * cs) * sizeof(bf16_t)) : OOB;
+            }
+            const unsigned d0 = wbase + slot * (unsigned)(kWgradDmaSlot * sizeof(bf16_t)), d1 = d0 + 32u * WDP * sizeof(bf16_t),
+                           d2 = d1 + 32u * WDP * sizeof(bf16_t);
+            asm volatile("s_nop 4\n\t"
+                         "s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %6, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %4, %7, 0 offen lds\n\t"
+                         "s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %5, %7, 0 offen lds"
+                         :: "s"(d0), "s"(d1), "s"(d2), "v"(og), "v"(ox[0]), "v"(ox[1]), "s"(dG), "s"(dX) : "memory");
+        };
+        // read offsets inside a slot (bf16): the swizzle term follows the tile row, so every tap has its own; + 4 and + 16 rows keep it
+        const int ra = trow * WDP + ((wm * 32 + tcol) ^ (8 * wdma_f(trow)));
+        int rb[WK];
+#pragma unroll
+        for (int j = 0; j < WK; ++j) rb[j] = (32 + trow + toff[j]) * WDP + ((wn * 32 + tcol) ^ (8 * wdma_f(trow + toff[j])));
+        const int bo = rr * WDP + 8 * cs;                   // the row's piece cg, for the bias sums
+        const int nch = (int)((re - rs + 31) / 32);
+        for (int c = 0; c < WNS - 1; ++c) issue(c, (unsigned)c);
+        auto run = [&](auto bias_c) __attribute__((always_inline)) {
+            constexpr bool BIAS = decltype(bias_c)::value;
+            unsigned slot = 0;                              // slot of chunk ch = ch % WNS
+            for (int ch = 0; ch < nch; ++ch) {
+                if (ch == 4) PSND_WSTAMP(5);
+                // this wave's transfers of chunk ch have landed (the WNS - 2 chunks behind it may still fly), its reads of chunk ch - 1 are done
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" :: "n"(3 * (WNS - 2)) : "memory");
+                if (ch == 0) PSND_WSTAMP(1);
+                if (ch == 4) PSND_WSTAMP(6);
+                __builtin_amdgcn_s_barrier();
+                if (ch == 4) PSND_WSTAMP(7);
+                issue(ch + WNS - 1, slot == 0 ? WNS - 1 : slot - 1);
+                const bf16_t *sS = sT + slot * kWgradDmaSlot;
+                bf16x8 fa[2], fb[2][WK];
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) {
+                    fa[kk] = tr_frag_dma(sS + 16 * kk * WDP + ra);
+#pragma unroll
+                    for (int j = 0; j < WK; ++j) fb[kk][j] = tr_frag_dma(sS + 16 * kk * WDP + rb[j]);
+                }
+                if constexpr (BIAS) {                       // the sums of the register-staged loop, in its order: row rr, channels 8 cg ..
+                    const uint4 g = *reinterpret_cast<const uint4 *>(sS + bo);
+                    const unsigned *pg4 = reinterpret_cast<const unsigned *>(&g);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bsum[e] += bf2f((bf16_t)((pg4[e >> 1] >> (16 * (e & 1))) & 0xffff));
+                }
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                    for (int j = 0; j < WK; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk][j], acc[j], 0, 0, 0);
+                slot = slot + 1 == WNS ? 0 : slot + 1;
+            }
+        };
+        if (do_bias) run(std::true_type{});                 // uniform per workgroup
+        else run(std::false_type{});
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the transfers past the range (zeros): the epilogue re-uses the ring
+    } else {
     // whole ring turns: chunks past the row range load and multiply zeros (at most WD - 1 of them)
     const int nchunk = ((int)((re - rs + 31) / 32) + WD - 1) / WD * WD;
     static_for<0, WD>([&](auto sc) __attribute__((always_inline)) { fetch(sc, rs + 32ll * decltype(sc)::value); });
@@ -957,6 +1072,7 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradParams &p, const int 
 #pragma unroll
                 for (int j = 0; j < WK; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk], fb[kk][j], acc[j], 0, 0, 0);
         });
+    }
     }
     __syncthreads();
     PSND_WSTAMP(2);
@@ -1038,10 +1154,27 @@ __device__ __forceinline__ void conv_wgrad_body(const WgradParams &p, const int 
     }
 #endif
 }
+// The plain body (no g_out, no transposed-conv view) of a launch.  DMA: what the launch takes - the LDS-DMA ring in the batched launch
+// (conv_wgrad_multi_kernel, three workgroups per CU: 73 -> 64 us in the config-2 step), the register-staged loop in the launches whose
+// weight-gradient workgroups sit alone on a CU (conv_wgrad_kernel at the 513-channel head conv 23 -> 30 us with the ring, the role of
+// conv_bwd_pair_kernel 25.5 -> 29 us: profiles/NOTEBOOK.md).  Lab builds carry both loops and PSND_WGRAD_STAGE=regs | dma picks one for
+// every launch (parity tests, same-box A/B timings); the product build has the launch's own loop only.
+template <bool DMA>
+__device__ __forceinline__ void conv_wgrad_plain(const WgradParams &p, const int bx, const int by, const int bz, bf16_t *sT, const size_t tblk) {
+#ifdef PSND_LAB
+    if (p.stage == 0 ? DMA : p.stage == 2) conv_wgrad_body<false, false, WKT, true>(p, bx, by, bz, sT, tblk);       // uniform
+    else conv_wgrad_body<false>(p, bx, by, bz, sT, tblk);
+#else
+    if constexpr (DMA) conv_wgrad_body<false, false, WKT, true>(p, bx, by, bz, sT, tblk);
+    else conv_wgrad_body<false>(p, bx, by, bz, sT, tblk);
+#endif
+}
 __global__ __launch_bounds__(256, PSND_WGRAD_WAVES) void conv_wgrad_kernel(WgradParams p) {
     extern __shared__ __attribute__((aligned(16))) bf16_t smem_dyn[];
-    if (p.G2) conv_wgrad_body<true>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-    else conv_wgrad_body<false>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn, ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+    const size_t tblk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (p.G2) conv_wgrad_body<true>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn, tblk);
+    else if (p.g_out || p.up_u > 0) conv_wgrad_body<false>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn, tblk);   // uniform
+    else conv_wgrad_plain<false>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn, tblk);
 }
 
 // The two independent kernels of a conv's backward - weight gradient (partial slabs) and input gradient (with the on-load
@@ -1058,7 +1191,9 @@ __global__ __launch_bounds__(256, (D == 1 ? 3 : PSND_CONV_OCC)) void conv_bwd_pa
     const int b = blockIdx.x;
     if (b < nw) {
         const int bx = b % wgx, r = b / wgx;
-        conv_wgrad_body<COMBINE, WN, ((WN || D == 1) ? WKT : pair_wk(KT, HMX))>(pw, bx, r % wgy, r / wgy, smem_dyn, 0);   // D == 1: the 168-VGPR instances
+        constexpr int WKP = (WN || D == 1) ? WKT : pair_wk(KT, HMX);                // D == 1: the 168-VGPR instances
+        if constexpr (!COMBINE && !WN && WKP == WKT) conv_wgrad_plain<false>(pw, bx, r % wgy, r / wgy, smem_dyn, 0);   // (no g_out, no transposed view here)
+        else conv_wgrad_body<COMBINE, WN, WKP>(pw, bx, r % wgy, r / wgy, smem_dyn, 0);
     } else {
         const int c = b - nw;
         conv_cl_body<KT, D, COMBINE, NBUF, MT, HMX, false, KCT, WNC>(pc, c % cgx, c / cgx, smem_dyn, 0);
@@ -1082,10 +1217,10 @@ __global__ __launch_bounds__(256, 2) void conv_pair_bwd_kernel(pairk::PairParams
     const int b = blockIdx.x;
     if (b < nwa) {
         const int bx = b % wgx, r = b / wgx;
-        conv_wgrad_body<false>(wa, bx, r % wgy, r / wgy, smem_dyn, 0);
+        conv_wgrad_plain<false>(wa, bx, r % wgy, r / wgy, smem_dyn, 0);
     } else if (b < nwa + nwb) {
         const int c = b - nwa, bx = c % wgx, r = c / wgx;
-        conv_wgrad_body<false>(wb_, bx, r % wgy, r / wgy, smem_dyn, 0);
+        conv_wgrad_plain<false>(wb_, bx, r % wgy, r / wgy, smem_dyn, 0);
     } else {
         pairk::conv_pair_body<256, PSND_PAIRBWD_MR, true, 4, PSND_PAIRBWD_RU>(pp, b - nwa - nwb, smem_dyn);
     }
@@ -1132,7 +1267,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_multi_kernel(WgradMultiArgs
     w.Ca = a.c[c].Ca, w.Cb = a.c[c].Cb, w.k = a.c[c].k, w.rows_per_split = a.c[c].rps;
     const int wgx = a.c[c].wgx, wgy = a.c[c].wgy, txy = t % (wgx * wgy), tgrp = t / (wgx * wgy);
     const int bx = a.ci_fastest ? txy / wgy : txy % wgx, by = a.ci_fastest ? txy % wgy : txy / wgx;
-    conv_wgrad_body<false>(w, bx, by, split * (a.c[c].tiles / (wgx * wgy)) + tgrp, smem_dyn, 0);
+    conv_wgrad_plain<true>(w, bx, by, split * (a.c[c].tiles / (wgx * wgy)) + tgrp, smem_dyn, 0);
 }
 
 // ---- weight prep: weight norm (dim 0) + both bf16 packs + padded bias, one block per output channel ------
@@ -1827,6 +1962,8 @@ static void conv_params_plain(ConvParams &p) {
 }
 static void wgrad_params_plain(WgradParams &p) {
     p.up_u = 0, p.up_p = 0, p.up_Lp = 0, p.up_HP = 0, p.up_LpO = 0, p.up_HPO = 0, p.up_Cr = 0;
+    const char *ws = PSND_ENV("PSND_WGRAD_STAGE");         // read per call: the parity tests flip it inside one process
+    p.stage = !ws ? 0 : (!strcmp(ws, "regs") ? 1 : (!strcmp(ws, "dma") ? 2 : 0));
 #ifdef PSND_TRACE
     p.trace = nullptr;
 #endif
@@ -2032,7 +2169,7 @@ extern "C" int psnd_conv1d_cl_wgrad(const void *G1, const void *G2, const void *
         p.trace = tp ? reinterpret_cast<long long *>(strtoull(tp, nullptr, 0)) : nullptr;
     }
 #endif
-    hipLaunchKernelGGL(conv_wgrad_kernel, dim3(tx, ty, (unsigned)(splits * ((k + WKT - 1) / WKT))), dim3(256), kWgradLdsBytes,
+    hipLaunchKernelGGL(conv_wgrad_kernel, dim3(tx, ty, (unsigned)(splits * ((k + WKT - 1) / WKT))), dim3(256), kWgradLaunchLdsBytes,
                        static_cast<hipStream_t>(stream), p);
     PSND_CHECK_LAUNCH("conv1d_cl_wgrad");
     return PSND_OK;
@@ -2125,7 +2262,7 @@ extern "C" int psnd_conv1d_cl_wgrad_multi(const psnd_wgrad_desc *d, int n, int64
     }
     if (!a.linear) total = 8 * *std::max_element(load, load + 8);
     if (total > 0x7fffffff) PSND_FAIL(PSND_E_SHAPE, "conv1d_cl_wgrad_multi: %lld workgroups", (long long)total);
-    hipLaunchKernelGGL(conv_wgrad_multi_kernel, dim3((unsigned)total), dim3(256), kWgradLdsBytes, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(conv_wgrad_multi_kernel, dim3((unsigned)total), dim3(256), kWgradMultiLdsBytes, static_cast<hipStream_t>(stream), a);
     PSND_CHECK_LAUNCH("conv1d_cl_wgrad_multi");
     return PSND_OK;
 }
@@ -2186,7 +2323,7 @@ extern "C" int psnd_conv1d_cl_pair_bwd(const void *G, const void *wb2, const voi
     pairk::PairParams pp;
     memset(&pp, 0, sizeof(pp));
     int tiles = 0;
-    size_t lds = kWgradLdsBytes;
+    size_t lds = kWgradLaunchLdsBytes;
     if (have_pair) {
         pp.A = static_cast<const pairk::bf16_t *>(G), pp.W1 = static_cast<const pairk::bf16_t *>(wb2), pp.W2 = static_cast<const pairk::bf16_t *>(wb1);
         pp.bias1 = nullptr, pp.bias2 = nullptr;
@@ -2285,7 +2422,7 @@ extern "C" int psnd_conv1d_cl_bwd(const void *G1, const void *G2, const void *GM
     const int kct = 32;
     size_t lds = 2 * sizeof(bf16_t) * (kct + 8) * (size_t)(bm + 2 * hm);
     if (lds < sizeof(float) * bm * (bn + 8)) lds = sizeof(float) * bm * (bn + 8);
-    if (lds < (size_t)kWgradLdsBytes) lds = kWgradLdsBytes;
+    if (lds < (size_t)kWgradLaunchLdsBytes) lds = kWgradLaunchLdsBytes;
     if (wn && lds < (size_t)kWgradNarrowLdsBytes) lds = kWgradNarrowLdsBytes;
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define PSND_PAIR_LAUNCH(KT_, D_, C_, H_)                                                                              \
@@ -2750,7 +2887,7 @@ extern "C" int psnd_convtr1d_cl_bwd(const void *g_raw, const void *g_act, const 
     int64_t rps;
     const int splits = wgrad_splits(w.R, w.Ca, w.Cb, 2, &rps);
     w.rows_per_split = (int)rps;
-    hipLaunchKernelGGL(conv_wgrad_kernel, dim3((w.Cb + 63) / 64, (w.Ca + 63) / 64, (unsigned)splits), dim3(256), kWgradLdsBytes, st, w);
+    hipLaunchKernelGGL(conv_wgrad_kernel, dim3((w.Cb + 63) / 64, (w.Ca + 63) / 64, (unsigned)splits), dim3(256), kWgradLaunchLdsBytes, st, w);
     PSND_CHECK_LAUNCH("convtr1d_cl_bwd(wgrad)");
     return PSND_OK;
 }
