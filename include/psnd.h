@@ -897,6 +897,58 @@ int psnd_mel_inverse_plan_build(int M, int K, const float *mel_filter_host, int 
 int psnd_mel_inverse(const float *mel, int64_t N, int64_t F, int M, int K, const void *plan, int log_kind, float log_offset, int n_iter,
                      const int64_t *frames, float *out, float *resid, void *stream);
 
+/* ---- loudness, plain levels and gain on device tensors (psnd_loudness.hip): the level normalisation of the reference's preprocessing
+ *  (scripts/preprocess.py:32-41 runs every file through ffmpeg-normalize on the host).  What is computed is ITU-R BS.1770-4 / EBU R128
+ *  integrated loudness as written out here; parity with ffmpeg's numbers is unpinned.
+ *  A programme is C >= 1 channels of T_r samples (fp32) at rate sr: rows n C .. n C + C - 1 of x : (N C, T).  Every programme on its own.
+ *    1  K-weighting.  Two sections of order 2 in series (shelf, then high-pass), each y[t] = b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1]
+ *       - a2 y[t-2] with zero state before t = 0, in fp64.  The ten coefficients are formed on the host in double for the given sr and passed
+ *       by value, so a call can be captured:
+ *         shelf      K = tan(pi f0 / sr), f0 = 1681.974450955533, Q = 0.7071752369554196, Vh = 10^(3.999843853973347 / 20),
+ *                    Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2), 2 (K^2 - Vh), (Vh - Vb K/Q + K^2)] / a0,
+ *                    a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0]
+ *         high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1], a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0] with
+ *                    its own K and a0
+ *       At 48 kHz: b = 1.53512485958697, -2.69169618940638, 1.19839281085285, a1, a2 = -1.69065929318241, 0.73248077421585; high-pass
+ *       a1, a2 = -1.99004745483398, 0.99007225036621 (the table of BS.1770, reproduced to 1e-13).
+ *    2  Blocks.  Block length B and hop H in samples, 1 <= H <= B, from the caller (the wrappers: B = round(0.4 sr), H = B / 4 rounded
+ *       down).  A row has J_r = (T_r - B) / H + 1 complete blocks, none if T_r < B.  z[j] = sum_c G_c (1/B) sum_{t in [jH, jH + B)} y_c[t]^2:
+ *       an fp64 sum of at most B + (one span) terms in a fixed order, never a difference of row-long prefixes.  weights: C doubles on the
+ *       HOST, read during the call and passed on by value, or NULL for G = 1, 1, 1, 1.41, 1.41 (C <= 5).
+ *    3  Gates, in the energy domain in fp64.  Ja = {j : z[j] > 10^((-70 + 0.691) / 10)}; Gamma = 0.1 mean_{Ja} z;
+ *       Jg = {j in Ja : z[j] > Gamma}; L = -0.691 + 10 log10(mean_{Jg} z), rounded once to fp32.  Ja empty (J_r = 0 included): L = -inf.
+ *       A programme that holds a non-finite sample before its length (in a complete block or not) has L = NaN and NaN in its J_r entries
+ *       of `blocks`; it changes no other programme's result.
+ *    4  Outputs.  lufs[N] fp32; blocks[N][Jmax] fp32 or NULL, Jmax = psnd_loudness_blocks(T, B, H): the z[j], 0 behind J_r; gain[N] fp32
+ *       or NULL: 10^((target - L) / 20) of the fp32 L, exactly 1 where L is -inf, NaN or +inf.
+ *  psnd_loudness: an exact time-parallel scan over both sections at once (state of four doubles, end states combine through the powers of
+ *  the 4 x 4 block-triangular matrix of the cascade: lanes by shuffles, waves through LDS, the spans of psnd_loudness_span() samples of a
+ *  row through a carry array and a launch boundary).  The filtered signal is never written: the second walk squares it in registers into
+ *  pieces cut at the multiples of H (and at those plus B mod H, where that is not 0), one fp64 partial per (row, span, piece), each stored
+ *  once; the last launch, one workgroup per programme, adds the pieces of a block across spans and channels in ascending order and runs
+ *  the two gated means as fixed-order reductions.  At most three launches, no atomics, no workgroup waits on another, nothing read back
+ *  by the host, the same bits on every run.
+ *    lengths : per-PROGRAMME valid lengths (device int64, N entries, clamped to [0, T]) or NULL.  x may start on any 4-byte boundary.
+ *    scratch : psnd_loudness_scratch_bytes(N, C, T, B, H) bytes, 16-byte aligned; every entry that is read has been written by the same call.
+ *  psnd_row_level: per programme rms_db = 10 log10(mean x^2) over its C rows (fp64 sum in a fixed order), peak_db = 20 log10(max |x|), and
+ *    gain = 10^((target - level) / 20) of the rms (of_peak = 0) or the peak (of_peak = 1); any of the three outputs may be NULL.  No samples
+ *    or digital silence: -inf and gain 1.  A non-finite sample: NaN, NaN and gain 1.  One launch, no atomics.
+ *  psnd_gain_rows: y[n][t] = x[n][t] gain[n / C] for t before the programme's length, y = x behind it; x == y is allowed.
+ *  PSND_E_ARG before anything is launched: B < 1, H < 1, H > B, C < 1, a non-finite coefficient, weight or target, C > 5 without weights,
+ *  N or T < 0, a NULL pointer with work to do; PSND_E_UNSUPPORTED: C > psnd_loudness_max_channels(); PSND_E_SHAPE: more than 2^31 - 1
+ *  workgroups.  N == 0 or T == 0: nothing to do.  psnd_loudness_span, psnd_loudness_max_channels, psnd_loudness_blocks and
+ *  psnd_loudness_scratch_bytes are host helpers (functions, as psnd_pv_pass, not macros). */
+int64_t psnd_loudness_span(void);
+int64_t psnd_loudness_max_channels(void);
+int64_t psnd_loudness_blocks(int64_t T, int64_t B, int64_t H);
+size_t psnd_loudness_scratch_bytes(int64_t N, int64_t C, int64_t T, int64_t B, int64_t H);
+int psnd_loudness(const float *x, int64_t N, int64_t C, int64_t T, const int64_t *lengths, double sb0, double sb1, double sb2, double sa1,
+                  double sa2, double hb0, double hb1, double hb2, double ha1, double ha2, int64_t B, int64_t H, const double *weights,
+                  double target, void *scratch, float *lufs, float *blocks, float *gain, void *stream);
+int psnd_row_level(const float *x, int64_t N, int64_t C, int64_t T, const int64_t *lengths, int of_peak, double target, float *rms_db,
+                   float *peak_db, float *gain, void *stream);
+int psnd_gain_rows(const float *x, int64_t N, int64_t C, int64_t T, const int64_t *lengths, const float *gain, float *y, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

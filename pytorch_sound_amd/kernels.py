@@ -2,9 +2,10 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder`, the `griffinlim*` functions and `mel_inverse` alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder`, the `griffinlim*` functions, `mel_inverse`, `loudness`, `level` and `apply_gain` alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
+import ctypes
 import math
 import os
 from pytorch_sound_amd import _switches as _sw
@@ -1476,6 +1477,289 @@ def silence_ranges(wav, min_silence_len, silence_thresh, seek_step=1, lengths=No
     with on(wav.device) as hip:
         hip.psnd_silence_ranges(xf, N, T, lengths, L, s, theta, scratch, count, ranges, cap)
     return count, ranges
+
+
+# ---- loudness (include/psnd.h: ITU-R BS.1770-4 / EBU R128 integrated loudness), plain levels, gain ----------------------------------------
+LOUDNESS_GATE = 10.0 ** ((-70.0 + 0.691) / 10.0)        # the absolute gate as a block energy
+LOUDNESS_WEIGHTS = (1.0, 1.0, 1.0, 1.41, 1.41)
+LEVEL_KINDS = ('rms', 'peak')
+
+
+def k_weighting(sr):
+    """((b, a) of the shelf, (b, a) of the high-pass) of the K-weighting at `sr` Hz in float64, a[0] = 1: the formulas of include/psnd.h,
+    which give the table of BS.1770 at 48 kHz"""
+    sr = float(sr)
+    if not (math.isfinite(sr) and sr > 0.0):
+        raise ValueError('loudness: sr=%r must be positive' % (sr,))
+    K = math.tan(math.pi * 1681.974450955533 / sr)
+    Q = 0.7071752369554196
+    Vh = 10.0 ** (3.999843853973347 / 20.0)
+    Vb = Vh ** 0.4996667741545416
+    a0 = 1.0 + K / Q + K * K
+    shelf = ([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0],
+             [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+    K = math.tan(math.pi * 38.13547087602444 / sr)
+    Q = 0.5003270373238773
+    a0 = 1.0 + K / Q + K * K
+    return shelf, ([1.0, -2.0, 1.0], [1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0])
+
+
+def loudness_block(sr):
+    """(B, H): the block of 400 ms and the hop of a quarter of it in samples, B = round(0.4 sr), H = B // 4"""
+    B = int(math.floor(0.4 * float(sr) + 0.5))
+    if B < 4:
+        raise ValueError('loudness: sr=%r is too low for a block of 400 ms' % (sr,))
+    return B, B // 4
+
+
+def loudness_blocks(T, B, H):
+    """psnd_loudness_blocks: the complete blocks of a row of T samples"""
+    return 0 if B < 1 or H < 1 or T < B else (T - B) // H + 1
+
+
+def loudness_span():
+    """psnd_loudness_span: the samples per workgroup, the one size the kernel's seams depend on"""
+    return int(lib().psnd_loudness_span())
+
+
+def _programmes(shape, channels, who):
+    """(leading shape, N, C, T) of an input (..., T) of mono rows, or (..., C, T) with channels=C"""
+    if len(shape) == 0:
+        raise _lib.PsndError('%s: the input needs a time axis' % who)
+    if channels is None:
+        C, lead = 1, tuple(shape[:-1])
+    else:
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or channels < 1:
+            raise ValueError('%s: channels=%r - a count, at least 1' % (who, channels))
+        C = int(channels)
+        if len(shape) < 2 or shape[-2] != C:
+            raise _lib.PsndError('%s: channels=%d expects an input (..., %d, T), got %s' % (who, C, C, tuple(shape)))
+        lead = tuple(shape[:-2])
+    return lead, math.prod(lead), C, int(shape[-1])
+
+
+def _loudness_weights(C, weights):
+    if weights is None:
+        if C > len(LOUDNESS_WEIGHTS):
+            raise _lib.PsndError('loudness: %d channels need explicit weights (the default covers %d)' % (C, len(LOUDNESS_WEIGHTS)))
+        return list(LOUDNESS_WEIGHTS[:C])
+    w = np.asarray(weights, dtype=np.float64).reshape(-1).tolist()
+    if len(w) != C or not all(math.isfinite(v) for v in w):
+        raise _lib.PsndError('loudness: weights=%r - %d finite numbers' % (weights, C))
+    return w
+
+
+def _host_lengths(lengths, N, T, who):
+    if lengths is None:
+        return [T] * N
+    v = np.asarray(lengths.detach().cpu() if isinstance(lengths, torch.Tensor) else lengths)
+    if v.dtype.kind not in 'iu' or v.size != N:
+        raise _lib.PsndError('%s: lengths must be %d integers, got %s %s' % (who, N, v.shape, v.dtype))
+    return [min(max(int(k), 0), T) for k in v.reshape(-1).tolist()]
+
+
+def _device_lengths(lengths, N, device, who):
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths)
+    if lengths.is_floating_point() or lengths.numel() != N:
+        raise _lib.PsndError('%s: lengths must be %d integers, got %s %s' % (who, N, tuple(lengths.shape), lengths.dtype))
+    return lengths.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+
+
+def loudness_gate(z):
+    """the two gates of BS.1770 on the block energies z (float64): L in LUFS as a Python float, -inf where no block passes the absolute gate"""
+    z = np.asarray(z, dtype=np.float64)
+    za = z[z > LOUDNESS_GATE]
+    if za.size == 0:
+        return -_INF
+    zg = za[za > 0.1 * za.mean()]
+    return -0.691 + 10.0 * math.log10(zg.mean())
+
+
+def gain_of_level(level, target):
+    """float32 gains 10^((target - level) / 20) of float32 levels in dB; exactly 1 where the level is not finite"""
+    level = np.asarray(level, dtype=np.float32)
+    with np.errstate(invalid='ignore', over='ignore'):
+        g = np.power(10.0, (float(target) - level.astype(np.float64)) / 20.0).astype(np.float32)
+    return np.where(np.isfinite(level), g, np.float32(1.0)).astype(np.float32)
+
+
+def loudness_host(x, sr, lengths=None, channels=None, weights=None, return_blocks=False):
+    """the definition of include/psnd.h in float64 numpy on an array (..., T), or (..., C, T) with channels=C: float32 LUFS of the leading
+    shape, and with return_blocks the block energies z[j] (leading shape, Jmax) in float32, 0 behind a row's blocks.  A programme that
+    holds a non-finite sample reads NaN."""
+    from scipy.signal import lfilter as host_lfilter
+    x = np.asarray(x)
+    lead, N, C, T = _programmes(x.shape, channels, 'loudness')
+    G = np.asarray(_loudness_weights(C, weights), dtype=np.float64)
+    (b1, a1), (b2, a2) = k_weighting(sr)
+    B, H = loudness_block(sr)
+    lens = _host_lengths(lengths, N, T, 'loudness')
+    Jmax = loudness_blocks(T, B, H)
+    rows = x.reshape(N, C, T)
+    lufs = np.full(N, -np.inf, dtype=np.float32)
+    blocks = np.zeros((N, Jmax), dtype=np.float32)
+    for n in range(N):
+        v = rows[n, :, :lens[n]].astype(np.float64)
+        J = loudness_blocks(lens[n], B, H)
+        if not np.isfinite(v).all():
+            lufs[n], blocks[n, :J] = np.nan, np.nan
+            continue
+        if J == 0:
+            continue
+        y = host_lfilter(b2, a2, host_lfilter(b1, a1, v, axis=-1), axis=-1)
+        e = np.lib.stride_tricks.sliding_window_view(y * y, B, axis=-1)[:, ::H].sum(axis=-1)           # (C, J)
+        z = (G[:, None] * e).sum(axis=0) / B
+        blocks[n, :J] = z
+        lufs[n] = loudness_gate(z)
+    lufs = lufs.reshape(lead)
+    return (lufs, blocks.reshape(lead + (Jmax,))) if return_blocks else lufs
+
+
+def level_host(x, kind, lengths=None, channels=None):
+    """float32 rms_db = 10 log10(mean x^2) or peak_db = 20 log10(max |x|) per programme in float64 numpy; -inf for silence or no samples,
+    NaN where a sample is not finite"""
+    if kind not in LEVEL_KINDS:
+        raise ValueError("level: kind=%r - 'rms' or 'peak'" % (kind,))
+    x = np.asarray(x)
+    lead, N, C, T = _programmes(x.shape, channels, 'level')
+    lens = _host_lengths(lengths, N, T, 'level')
+    rows = x.reshape(N, C, T)
+    out = np.full(N, -np.inf, dtype=np.float32)
+    for n in range(N):
+        v = rows[n, :, :lens[n]].astype(np.float64)
+        if not np.isfinite(v).all():
+            out[n] = np.nan
+        elif v.size and np.abs(v).max() > 0.0:
+            out[n] = 10.0 * math.log10(float((v * v).sum()) / v.size) if kind == 'rms' else 20.0 * math.log10(float(np.abs(v).max()))
+    return out.reshape(lead)
+
+
+def apply_gain_host(x, gain, lengths=None, channels=None):
+    """float32 x gain[programme] before the programme's length, x behind it (numpy)"""
+    x = np.asarray(x)
+    lead, N, C, T = _programmes(x.shape, channels, 'apply_gain')
+    g = np.asarray(gain, dtype=np.float32).reshape(-1)
+    if g.size != N:
+        raise _lib.PsndError('apply_gain: %d gains for %d programmes' % (g.size, N))
+    lens = np.asarray(_host_lengths(lengths, N, T, 'apply_gain'), dtype=np.int64)
+    xf = x.reshape(N, C, T).astype(np.float32)
+    live = np.arange(T)[None, None, :] < lens[:, None, None]
+    return np.where(live, xf * g[:, None, None], xf).astype(np.float32).reshape(x.shape)
+
+
+def _meter_rows(wav, channels, who):
+    """a HIP tensor as (N C, T) float32 rows the kernels can walk (any 4-byte start, unit stride in time, rows T apart), with its geometry"""
+    if not isinstance(wav, torch.Tensor) or not wav.is_cuda:
+        raise _lib.PsndError('%s: a HIP tensor is expected here (CPU tensors and numpy arrays take the host path of the public function)' % who)
+    lead, N, C, T = _programmes(wav.shape, channels, who)
+    if not wav.is_floating_point():
+        raise _lib.PsndError('%s: floating input expected, got %s' % (who, wav.dtype))
+    xf = wav.detach().reshape(N * C, T)
+    if xf.dtype != torch.float32:
+        xf = xf.float()
+    if N * C * T > 0 and (xf.stride(-1) != 1 or (N * C > 1 and xf.stride(0) != T)):
+        xf = xf.contiguous()
+    return xf, lead, N, C, T
+
+
+def loudness_gain(wav, sr, target=-23.0, lengths=None, channels=None, weights=None, return_blocks=False):
+    """one call of psnd_loudness on a HIP tensor: (lufs, gain, blocks or None) - float32 LUFS and the gains 10^((target - lufs) / 20), both of
+    the leading shape (gain 1 where the loudness is not finite), and the block energies (leading shape, Jmax)"""
+    xf, lead, N, C, T = _meter_rows(wav, channels, 'loudness')
+    G = _loudness_weights(C, weights)
+    (b1, a1), (b2, a2) = k_weighting(sr)
+    B, H = loudness_block(sr)
+    lengths = _device_lengths(lengths, N, wav.device, 'loudness')
+    Jmax = loudness_blocks(T, B, H)
+    dev = wav.device
+    if N * T == 0:                                       # nothing to launch: no blocks, no loudness
+        blocks = torch.zeros(lead + (Jmax,), dtype=torch.float32, device=dev) if return_blocks else None
+        return torch.full(lead, -_INF, dtype=torch.float32, device=dev), torch.ones(lead, dtype=torch.float32, device=dev), blocks
+    lufs = torch.empty(N, dtype=torch.float32, device=dev)
+    gain = torch.empty(N, dtype=torch.float32, device=dev)
+    blocks = torch.empty((N, Jmax), dtype=torch.float32, device=dev) if return_blocks else None
+    scratch = torch.empty(int(lib().psnd_loudness_scratch_bytes(N, C, T, B, H)), dtype=torch.uint8, device=dev)
+    with on(dev) as hip:
+        hip.psnd_loudness(xf, N, C, T, lengths, b1[0], b1[1], b1[2], a1[1], a1[2], b2[0], b2[1], b2[2], a2[1], a2[2], B, H,
+                          (ctypes.c_double * C)(*G), float(target), scratch, lufs, blocks, gain)
+    return lufs.reshape(lead), gain.reshape(lead), (blocks.reshape(lead + (Jmax,)) if return_blocks else None)
+
+
+def loudness(wav, sr, lengths=None, channels=None, weights=None, return_blocks=False):
+    """integrated loudness in LUFS (ITU-R BS.1770-4 / EBU R128, the definition of include/psnd.h) of every programme of `wav`: float32 of
+    the leading shape.  `wav` is (..., T), every row a mono programme, or (..., C, T) with channels=C; `weights`: C channel weights
+    (default 1, 1, 1, 1.41, 1.41 for C <= 5); `lengths`: per-programme valid lengths, clamped to [0, T].  return_blocks: also the block
+    energies z[j] (leading shape, Jmax) float32 - the momentary curve is -0.691 + 10 log10 z.  -inf for a programme that is silent or
+    shorter than a block of 400 ms, NaN for one that holds a non-finite sample.
+
+    HIP tensors run psnd_loudness (float32 samples; other float dtypes are cast) with no host synchronisation - the call can be captured;
+    CPU tensors and numpy arrays go through `loudness_host` in float64.  No autograd: the meter is not differentiated."""
+    if isinstance(wav, torch.Tensor) and wav.is_cuda:
+        lufs, _, blocks = loudness_gain(wav, sr, -23.0, lengths, channels, weights, return_blocks)
+        return (lufs, blocks) if return_blocks else lufs
+    tensor = isinstance(wav, torch.Tensor)
+    x = wav.detach().numpy() if tensor and wav.dtype != torch.bfloat16 else (wav.detach().float().numpy() if tensor else wav)
+    r = loudness_host(x, sr, lengths, channels, weights, return_blocks)
+    if not tensor:
+        return r
+    return (torch.from_numpy(r[0].copy()), torch.from_numpy(r[1].copy())) if return_blocks else torch.from_numpy(np.array(r))
+
+
+def level_gain(wav, kind, target=0.0, lengths=None, channels=None):
+    """one call of psnd_row_level on a HIP tensor: (level in dB, gain 10^((target - level) / 20)), float32 of the leading shape"""
+    if kind not in LEVEL_KINDS:
+        raise ValueError("level: kind=%r - 'rms' or 'peak'" % (kind,))
+    xf, lead, N, C, T = _meter_rows(wav, channels, 'level')
+    lengths = _device_lengths(lengths, N, wav.device, 'level')
+    db = torch.empty(N, dtype=torch.float32, device=wav.device)
+    gain = torch.empty(N, dtype=torch.float32, device=wav.device)
+    if N > 0:
+        with on(wav.device) as hip:
+            hip.psnd_row_level(xf, N, C, T, lengths, int(kind == 'peak'), float(target), db if kind == 'rms' else None,
+                               db if kind == 'peak' else None, gain)
+    return db.reshape(lead), gain.reshape(lead)
+
+
+def level(wav, kind, lengths=None, channels=None):
+    """the plain level of every programme of `wav` in dB re full scale, float32 of the leading shape: kind 'rms' 10 log10(mean x^2) over the
+    programme's channels and samples, 'peak' 20 log10(max |x|) (the sample peak, not the oversampled true peak).  -inf for silence, NaN
+    where a sample is not finite.  Shapes, `lengths`, `channels` and devices as `loudness`; HIP tensors run psnd_row_level."""
+    if isinstance(wav, torch.Tensor) and wav.is_cuda:
+        return level_gain(wav, kind, 0.0, lengths, channels)[0]
+    tensor = isinstance(wav, torch.Tensor)
+    r = level_host(wav.detach().float().numpy() if tensor and wav.dtype == torch.bfloat16 else (wav.detach().numpy() if tensor else wav),
+                   kind, lengths, channels)
+    return torch.from_numpy(np.array(r)) if tensor else r
+
+
+def apply_gain(wav, gain, lengths=None, channels=None, out=None):
+    """`wav` with every programme multiplied by its entry of `gain` (one per programme, read from device memory on a HIP tensor: no host
+    round trip); samples behind `lengths` are copied unchanged.  Comes back in wav's dtype.  out: a float32 HIP tensor of wav's shape to
+    write into, `wav` itself for in place (float32, contiguous rows).  CPU tensors and numpy arrays go through numpy."""
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
+        if out is not None:
+            raise _lib.PsndError('apply_gain: out= is for HIP tensors')
+        tensor = isinstance(wav, torch.Tensor)
+        g = gain.detach().cpu().numpy() if isinstance(gain, torch.Tensor) else gain
+        y = apply_gain_host(wav.detach().float().numpy() if tensor else wav, g, lengths, channels)
+        return torch.from_numpy(y).to(wav.dtype) if tensor else y
+    xf, lead, N, C, T = _meter_rows(wav, channels, 'apply_gain')
+    gain = torch.as_tensor(gain, dtype=torch.float32, device=wav.device).reshape(-1).contiguous()
+    if gain.numel() != N:
+        raise _lib.PsndError('apply_gain: %d gains for %d programmes' % (gain.numel(), N))
+    lengths = _device_lengths(lengths, N, wav.device, 'apply_gain')
+    if out is None:
+        y = torch.empty((N * C, T), dtype=torch.float32, device=wav.device)
+    else:
+        if out.dtype != torch.float32 or out.shape != wav.shape or not out.is_cuda or not out.is_contiguous():
+            raise _lib.PsndError('apply_gain: out must be a contiguous float32 HIP tensor of the shape %s' % (tuple(wav.shape),))
+        y = out
+    if N * C * T > 0:
+        with on(wav.device) as hip:
+            hip.psnd_gain_rows(xf, N, C, T, lengths, gain, y)
+    return out if out is not None else y.reshape(wav.shape).to(wav.dtype)
 
 
 def _count(name, v, least):

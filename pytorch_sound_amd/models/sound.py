@@ -224,6 +224,29 @@ class PitchShift(torch.nn.Module):
         return 'sr=%r, n_steps=%r, bins_per_octave=%r, p=%d, q=%d' % (self.sr, self.n_steps, self.bins_per_octave, self.p, self.q)
 
 
+class LoudnessNorm(torch.nn.Module):
+    """``utils.sound.normalize`` as a module on (B, T) or (B, 1, T), no parameters: every row scaled by one gain to ``target_level`` - LUFS
+    (ITU-R BS.1770-4 / EBU R128 integrated loudness, include/psnd.h) for kind 'ebu', dB re full scale of the rms / the sample peak for
+    'rms' / 'peak'.  The place of the reference's offline ffmpeg-normalize pass (scripts/preprocess.py:32-41); parity with it is
+    unpinned.  A silent or too-short row comes back unchanged.  On a HIP tensor nothing is read back by the host: a call can be captured.
+    ``lengths``: per-row valid lengths.  No gradient."""
+
+    def __init__(self, sr: int, target_level: float = -23.0, kind: str = 'ebu'):
+        super().__init__()
+        from pytorch_sound_amd.utils import sound as U
+        if kind not in U.NORMALIZE_KINDS:
+            raise ValueError("LoudnessNorm: kind=%r - 'ebu', 'rms' or 'peak'" % (kind,))
+        K.k_weighting(sr), K.loudness_block(sr)
+        self.sr, self.target_level, self.kind = sr, float(target_level), kind
+
+    def forward(self, wav: torch.Tensor, lengths=None) -> torch.Tensor:
+        from pytorch_sound_amd.utils import sound as U
+        return U.normalize(_wave_rows(wav, 'LoudnessNorm'), self.sr, self.target_level, self.kind, lengths)
+
+    def extra_repr(self) -> str:
+        return 'sr=%r, target_level=%r, kind=%r' % (self.sr, self.target_level, self.kind)
+
+
 class GriffinLim(torch.nn.Module):
     """``kernels.griffinlim`` as a module on magnitudes (N, K, F) or (K, F) with K = n_fft // 2 + 1, no parameters: ``n_iter`` iterations
     of fast Griffin-Lim (torchaudio's / librosa's definition, include/psnd.h), (F - 1) hop_length samples per item.  ``power``: the

@@ -8,6 +8,8 @@
                                    pysndfx's AudioEffectsChain)
     griffinlim                     a waveform from a magnitude spectrogram alone (the reference has none; it imports librosa throughout)
     mel_to_magnitude, mel_to_wave  a linear magnitude, and a waveform, from a mel spectrogram alone (the reference has none)
+    loudness, normalize            integrated loudness in LUFS and level normalisation (the reference runs every file through
+                                   ffmpeg-normalize on the host: scripts/preprocess.py:32-41)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -47,6 +49,15 @@ the host transforms.  No early stopping, no gradient.
 filterbank, a fixed number of FISTA steps from a flat-band guess - one launch of psnd_mel_inverse.hip on a HIP tensor, float64 numpy on
 numpy arrays and CPU tensors.  torchaudio's `InverseMelScale` and librosa's `mel_to_stft` are other algorithms: parity unpinned.
 `mel_to_wave` is `mel_to_magnitude` followed by `griffinlim`.  No gradient.
+
+`loudness` and `normalize` are NOT pinned against the reference either: parity with ffmpeg-normalize's numbers is UNPINNED, because this
+project cannot run ffmpeg.  What is implemented is the loudness section of include/psnd.h: ITU-R BS.1770-4 / EBU R128 integrated loudness
+(K-weighting re-derived for the rate at hand, blocks of 400 ms every 100 ms, the absolute gate at -70 LUFS and the relative gate 10 LU
+below the ungated mean), and for kind 'rms' / 'peak' the plain level 10 log10(mean x^2) / 20 log10(max |x|) - 'rms' is the mode
+`process_all` asks ffmpeg-normalize for.  No oversampled true peak, no short-term loudness, no loudness range, no limiter: a gain only.
+On a HIP tensor the meter is psnd_loudness.hip (one read of every sample per launch, the filtered signal never written) and the gain is
+applied from device memory: no host round trip, a call can be captured; numpy arrays and CPU tensors run the same definition in float64
+numpy.  The tests check known answers (a 997 Hz sine at 0 dBFS reads -3.01 LUFS) and a sequential yardstick.  No gradient.
 """
 import math
 
@@ -276,6 +287,49 @@ def mel_to_wave(mel, mel_filter, n_fft=None, hop_length=None, n_iter=64, gl_iter
     n_fft // 4.  Two calls of the library's loops on a HIP tensor, nothing leaves the device.  No gradient."""
     mag = mel_to_magnitude(mel, mel_filter, n_iter, log, log_offset)
     return griffinlim(mag, gl_iter, n_fft, hop_length, momentum, length, None, rand_init)
+
+
+def loudness(wav, sr, lengths=None, channels=None, weights=None, return_blocks=False):
+    """integrated loudness in LUFS of every programme of `wav` at `sr` Hz (ITU-R BS.1770-4 / EBU R128, include/psnd.h): float32 of the
+    leading shape, numpy in -> numpy out, tensor in -> tensor on the same device out.  `wav` is (..., T), every row a mono programme, or
+    (..., C, T) with channels=C (weights default to 1, 1, 1, 1.41, 1.41).  -inf: silent or shorter than 400 ms; NaN: a non-finite sample.
+    `kernels.loudness` does the work.  Parity with ffmpeg's ebur128 is unpinned: module docstring."""
+    return kernels.loudness(wav, sr, lengths, channels, weights, return_blocks)
+
+
+NORMALIZE_KINDS = ('ebu', 'rms', 'peak')
+
+
+def normalize(wav, sr, target_level=-23.0, kind='ebu', lengths=None, channels=None):
+    """`wav` with every programme scaled by one gain so that it measures `target_level`: LUFS for kind 'ebu' (`loudness`), dB re full
+    scale of its rms for 'rms' and of its sample peak for 'peak' (`sr` enters for 'ebu' only).  A programme whose level is not finite -
+    silent, shorter than a block of 400 ms ('ebu'), holding a non-finite sample - comes back unchanged; samples behind `lengths` are
+    copied.  No limiter: the result may exceed full scale.  numpy in -> float32 numpy out; tensor in -> tensor of the same dtype and
+    device out; on a HIP tensor two native calls (the meter, then the gain read from device memory), no host round trip, capturable.
+    No gradient (a tensor that requires grad comes back detached, as from `time_stretch`).  Parity with ffmpeg-normalize is unpinned:
+    module docstring."""
+    import torch
+    if kind not in NORMALIZE_KINDS:
+        raise ValueError("normalize: kind=%r - 'ebu', 'rms' or 'peak'" % (kind,))
+    target = float(target_level)
+    if not math.isfinite(target):
+        raise ValueError('normalize: target_level=%r' % (target_level,))
+    if _is_tensor(wav) and wav.is_cuda:
+        with torch.no_grad():
+            if kind == 'ebu':
+                gain = kernels.loudness_gain(wav, sr, target, lengths, channels)[1]
+            else:
+                gain = kernels.level_gain(wav, kind, target, lengths, channels)[1]
+            return kernels.apply_gain(wav, gain, lengths, channels)
+    if _is_tensor(wav):
+        if not wav.is_floating_point():
+            raise kernels.PsndError('normalize: floating input expected, got %s' % wav.dtype)
+        x = wav.detach().to(torch.float64).numpy()
+    else:
+        x = np.asarray(wav)
+    level = kernels.loudness_host(x, sr, lengths, channels) if kind == 'ebu' else kernels.level_host(x, kind, lengths, channels)
+    y = kernels.apply_gain_host(x, kernels.gain_of_level(level, target), lengths, channels)
+    return torch.from_numpy(y).to(wav.dtype) if _is_tensor(wav) else y
 
 
 def get_wav_duration(file):
