@@ -949,6 +949,73 @@ int psnd_row_level(const float *x, int64_t N, int64_t C, int64_t T, const int64_
                    float *peak_db, float *gain, void *stream);
 int psnd_gain_rows(const float *x, int64_t N, int64_t C, int64_t T, const int64_t *lengths, const float *gain, float *y, void *stream);
 
+/* ---- separation metrics on device tensors (psnd_separation.hip): SNR, SI-SDR and SD-SDR (Le Roux et al., "SDR - half-baked or well
+ *  done?") as values and as a loss, with permutation-invariant matching (PIT), their gradient, and mixing at a wanted SNR.  The
+ *  reference names the tasks (VoiceBank, DSD100 / MUSDB18 / MedleyDB, make_background_numpy of scripts/preprocess.py) and has no metric.
+ *  An item b of B holds S >= 1 estimates e_i and S targets s_j: est, target : (B, S, T) fp32, row-contiguous, rows may start on any
+ *  4-byte boundary.  Only samples t < L_b count: lengths is a device int64[B], clamped to [0, T], or NULL for L_b = T.
+ *    1  Moments.  fp64 sums in a fixed order over t < L:  Se_i = sum e_i, Ss_j = sum s_j, See_i = sum e_i^2, Sss_j = sum s_j^2,
+ *       Ses_ij = sum e_i s_j for every pair.  A product of two fp32 values is exact in fp64: the only rounding is in the additions.
+ *       With zero_mean = 1 the centred moments are formed from these, ee = See - Se^2 / L, ss = Sss - Ss^2 / L, es = Ses - Se Ss / L;
+ *       with zero_mean = 0, ee = See, ss = Sss, es = Ses.  L = 0 leaves them 0; a centred ee or ss below 0 (rounding, on a constant row) is 0.
+ *    2  Pair value of (i, j) from ee = ee_i, ss = ss_j, es = es_ij with eps >= 0 passed by value (the wrappers: fp32 machine epsilon,
+ *       torchmetrics' choice).  kind is a plain int, no macro:
+ *         0 snr     N = ss - 2 es + ee;                                       v = 10 log10((ss + eps) / (N + eps))
+ *         1 si_sdr  a = (es + eps) / (ss + eps); Tg = a^2 ss; N = Tg - 2 a es + ee;   v = 10 log10((Tg + eps) / (N + eps))
+ *         2 sd_sdr  a and Tg as above;           N = ss - 2 es + ee;          v = 10 log10((Tg + eps) / (N + eps))
+ *       N is clamped at 0 from below before eps is added.  All in fp64; v is rounded once to fp32.  (0 / 0 with eps = 0 reads NaN.)
+ *    3  Matching.  pit = 0: estimate i is matched with target i (only the diagonal is formed unless `pair` is asked for).  pit = 1: the
+ *       permutation p that maximises sum_i v[i][p(i)] - the fp32 values, added in fp64 in ascending i - among the S! permutations walked
+ *       in lexicographic order; a later one wins only by a strictly larger sum, so ties go to the lexicographically first.
+ *       S <= psnd_sep_max_sources() (4).  An item with a non-finite sample before its length gets NaN in all its values (its row of
+ *       `pair` included) and the identity permutation; it changes no other item's result.
+ *    4  Outputs.  value[B][S] fp32: v[i][p(i)];  perm[B][S] int32: p;  pair[B][S][S] fp32 or NULL: the whole matrix v[i][j];
+ *       loss[1] fp32 or NULL: -(1 / (B S)) sum value, added in fp64 in a fixed order;  nan_flag[1] fp32 or NULL: 1 where that sum is NaN,
+ *       else 0, written by the launch that forms the loss;  stats: psnd_sep_stats_doubles(B, S) doubles owned by the caller, kept for the
+ *       backward - per item S^2 + 4 S + 2 of them: Se[S], Ss[S], See[S], Sss[S], Ses[S][S], L, and 1.0 where the item is non-finite.
+ *  psnd_sep_metric_fwd.  Launch 1: a workgroup reads one span of psnd_sep_span() samples of all 2 S rows of an item once - a scalar head
+ *  up to the first 16-byte boundary of the item's first estimate row, 16-byte loads, a scalar tail; a row whose start is not congruent
+ *  to that row's modulo 16 bytes is read by the same 16-byte loads at 4-byte aligned addresses - with the S^2 + 4 S accumulators of a
+ *  lane in registers as fp64; lanes reduce by shuffles, waves through LDS, and one partial per (item, span, moment) is stored exactly
+ *  once.  Launch 2, one wave per item: the partials in ascending span order, the pair matrix, the permutations, value / perm / pair /
+ *  stats.  Launch 3 (only where loss or nan_flag is asked for): the loss and the flag.  At most three launches, no atomics, no workgroup
+ *  waits on another, nothing read back by the host, the same bits on every run of the same call (the order of the additions depends on
+ *  the addresses modulo 16 bytes, on T and on the lengths, on nothing else).  The longest serial run of additions is span / 256 + 1
+ *  in a lane, the tree above it is 6 + 3 deep, and the spans of a row follow serially: m + d = ceil(T / span) + 42.
+ *    scratch : psnd_sep_scratch_bytes(B, S, T) bytes, 8-byte aligned; every entry that is read has been written by the same call.
+ *  psnd_sep_metric_bwd.  One elementwise launch.  With G[b][i] = g_value[b][i] - g_loss / (B S) (either pointer may be NULL, not both;
+ *  g_loss is a device fp32 scalar) it writes g_est[b][i][t] = G (A e_i[t] + Bc s_p(i)[t] + C) and, where g_target is not NULL,
+ *  g_target[b][p(i)][t] = G (A' e_i[t] + B' s_p(i)[t] + C') for t < L and exactly 0 behind L: every element once.  L is the one the
+ *  forward kept in `stats`.  The six coefficients
+ *  are the derivatives of the formulas of 2 (eps takes part in a; the clamp passes the gradient where N >= 0) formed in fp64 from `stats`
+ *  and `perm` in device memory; C, C' != 0 only with zero_mean.  The rows of a non-finite item get NaN before L.
+ *  Mixing at an SNR (torchaudio's add_noise).  psnd_snr_gain: g[r] = sqrt(sum x^2 / sum z^2) 10^(-snr / 20) over t < L_r in fp64,
+ *  rounded to fp32, from launch 1 above with S = 1 plus one small launch; snr is a device fp32[R] (snr_n = R) or one device value
+ *  (snr_n = 1).  g = 0 where sum z^2 = 0, where sum x^2 = 0, or where either row holds a non-finite sample before L.
+ *  scratch: psnd_sep_scratch_bytes(R, 1, T).  psnd_mix_rows: y[r][t] = fmaf(g[r], z[r][t], x[r][t]) for t < L_r and y = x behind it (and everywhere where g[r] = 0);
+ *  x == y is allowed: the sibling of psnd_gain_rows.
+ *  PSND_E_ARG before anything is launched: a kind outside 0..2, zero_mean or pit outside 0..1, eps < 0 or not finite, S < 1, B or T < 0,
+ *  snr_n that is neither 1 nor R, a NULL pointer with work to do, a scratch that is not 8-byte aligned; PSND_E_UNSUPPORTED:
+ *  S > psnd_sep_max_sources(); PSND_E_SHAPE: more than 2^31 - 1 workgroups.  B == 0 or T == 0 (R == 0 for the mixing pair): nothing is
+ *  launched and no output is touched, except that a requested loss is set to 0 - the empty sum - and a requested nan_flag to 0, by a
+ *  memset on the stream.  psnd_sep_span, psnd_sep_max_sources, psnd_sep_scratch_bytes and psnd_sep_stats_doubles are host helpers
+ *  (functions, not macros).
+ *  Out of scope: BSS-eval SDR with a distortion filter (mir_eval, torchmetrics' signal_distortion_ratio), PESQ / STOI, Hungarian
+ *  matching for large S, multichannel items. */
+int64_t psnd_sep_span(void);
+int64_t psnd_sep_max_sources(void);
+size_t psnd_sep_scratch_bytes(int64_t B, int64_t S, int64_t T);
+int64_t psnd_sep_stats_doubles(int64_t B, int64_t S);
+int psnd_sep_metric_fwd(const float *est, const float *target, int64_t B, int64_t S, int64_t T, const int64_t *lengths, int kind,
+                        int zero_mean, double eps, int pit, void *scratch, double *stats, float *value, int *perm, float *pair, float *loss,
+                        float *nan_flag, void *stream);
+int psnd_sep_metric_bwd(const float *est, const float *target, int64_t B, int64_t S, int64_t T, int kind, int zero_mean, double eps,
+                        const double *stats, const int *perm, const float *g_loss, const float *g_value, float *g_est, float *g_target,
+                        void *stream);
+int psnd_snr_gain(const float *x, const float *z, int64_t R, int64_t T, const int64_t *lengths, const float *snr, int64_t snr_n,
+                  void *scratch, float *gain, void *stream);
+int psnd_mix_rows(const float *x, const float *z, int64_t R, int64_t T, const int64_t *lengths, const float *gain, float *y, void *stream);
+
 /* ---- fp32 instance of the Conv1d / ConvTranspose1d stack (models/vocoders/hifi_gan.py:32-147 computes its convolutions in fp32) -------
  *  A convolution = psnd_linear1x1_fwd (exact fp32 matrix-core GEMM) over the unfolded input
  *      col[n][ci * k + j][t] = act(x[n][ci][src]),  s' = t * stride + j * dil - pad,  src = s' / up  (0 where s' < 0, s' % up != 0 or src >= T),

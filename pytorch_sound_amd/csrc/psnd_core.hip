@@ -10,7 +10,7 @@ void psnd_set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int psnd_version(void) { return 151; }  // 0.1.51: + psnd_loudness, psnd_loudness_span / _max_channels / _blocks / _scratch_bytes, psnd_row_level, psnd_gain_rows (BS.1770 integrated loudness, plain levels, per-programme gain); 0.1.50: + psnd_mel_inverse, psnd_mel_inverse_plan_bytes / _plan_build, psnd_mel_inverse_tile, psnd_mel_inverse_max_iter (mel to linear magnitude: per-frame non-negative least squares by FISTA, the whole loop in one launch: psnd_mel_inverse.hip); 0.1.49: + psnd_griffinlim_start, psnd_griffinlim_step, psnd_gl_chunk, psnd_gl_chunks (Griffin-Lim: the start and the phase step between the two transforms, one launch each: psnd_griffinlim.hip); 0.1.48: + psnd_phase_vocoder, psnd_pv_frames, psnd_pv_pass (time-scale modification of a complex spectrogram, phase as a fixed-point fraction of a turn, one launch: psnd_phase_vocoder.hip); 0.1.47: + psnd_yin_f0, psnd_yin_frames, psnd_yin_max_span (YIN pitch per frame, one launch: psnd_pitch.hip); 0.1.46: + psnd_silence_ranges, psnd_silence_cap / _starts / _scratch_bytes (silent ranges per row from block-local fp64 window energies, three launches: psnd_silence.hip); 0.1.45: + psnd_resample, psnd_resample_len (sample-rate conversion by a rational factor and its adjoint, one polyphase kernel: psnd_resample.hip); 0.1.44: + psnd_lfilter, psnd_lfilter_spans (first- and second-order recursive filter sections as an exact scan parallel over time, both directions: psnd_lfilter.hip); 0.1.43: + psnd_istft_reim / _reim_mr / _reim_bwd (masked inverse STFT on (re, im), native in both directions); 0.1.42: + psnd_adam_step_sched (the learning rate of an in-flight step chosen on the device by the count of steps that succeeded: LR schedulers on the Trainer's device-skip path); 0.1.41: + psnd_stft_mr_* / psnd_istft_mr (mixed-radix STFT forward, backward, inverse for even n_fft = 2^a 3^b 5^c up to 4096: psnd_stft_mr.hip); 0.1.40: + psnd_ipreemph_fwd / _bwd, psnd_volnorm_fwd / _reverse (InversePreEmphasis as a scan parallel over time, VolNormConv per hop: psnd_sound.hip); 0.1.39: + psnd_groupnorm1_drop_fwd / _drop_bwd, psnd_rng_seed / psnd_rng_next (dropout formed inside the GroupNorm kernels, Philox4x32-10 mask, device-side {seed, call}); 0.1.38: + psnd_lstft_* (LearnableSTFT: strided-view analysis, polyphase synthesis, slab basis gradient); 0.1.37: psnd_groupnorm1_* take 2 C doubles of scratch per sample (one pair of sums per row: no atomics; round 6); 0.1.36: + psnd_linear1x1_fwd_ex, psnd_linear1x1_bwd_ex takes io_h (round 6: the hidden tensor of Conv1d -> ReLU -> Conv1d stored as bf16 under autocast); 0.1.35: + psnd_linear1x1_bwd_ex (round 6: the ReLU between two projections masks in the producing GEMM); 0.1.34: + psnd_im2col_f32 / psnd_col2im_f32 (round 6: the fp32 instance of the conv stack); 0.1.33: + psnd_cl_colsum, psnd_grad_pack_bf16 / _unpack_bf16 (round 5); 0.1.32: + psnd_mha_bwd_parts, psnd_convtr1d_cl_bwd takes either role alone (round 4); 0.1.31: psnd_mha_fwd / _bwd take `bf16` (round 3); 0.1.30: + psnd_polar_bwd, psnd_grad_sumsq
+extern "C" int psnd_version(void) { return 152; }  // 0.1.52: + psnd_sep_metric_fwd / _bwd, psnd_sep_span / _max_sources / _scratch_bytes / _stats_doubles, psnd_snr_gain, psnd_mix_rows (SNR / SI-SDR / SD-SDR with permutation-invariant matching, their gradient, mixing at an SNR: psnd_separation.hip); 0.1.51: + psnd_loudness, psnd_loudness_span / _max_channels / _blocks / _scratch_bytes, psnd_row_level, psnd_gain_rows (BS.1770 integrated loudness, plain levels, per-programme gain); 0.1.50: + psnd_mel_inverse, psnd_mel_inverse_plan_bytes / _plan_build, psnd_mel_inverse_tile, psnd_mel_inverse_max_iter (mel to linear magnitude: per-frame non-negative least squares by FISTA, the whole loop in one launch: psnd_mel_inverse.hip); 0.1.49: + psnd_griffinlim_start, psnd_griffinlim_step, psnd_gl_chunk, psnd_gl_chunks (Griffin-Lim: the start and the phase step between the two transforms, one launch each: psnd_griffinlim.hip); 0.1.48: + psnd_phase_vocoder, psnd_pv_frames, psnd_pv_pass (time-scale modification of a complex spectrogram, phase as a fixed-point fraction of a turn, one launch: psnd_phase_vocoder.hip); 0.1.47: + psnd_yin_f0, psnd_yin_frames, psnd_yin_max_span (YIN pitch per frame, one launch: psnd_pitch.hip); 0.1.46: + psnd_silence_ranges, psnd_silence_cap / _starts / _scratch_bytes (silent ranges per row from block-local fp64 window energies, three launches: psnd_silence.hip); 0.1.45: + psnd_resample, psnd_resample_len (sample-rate conversion by a rational factor and its adjoint, one polyphase kernel: psnd_resample.hip); 0.1.44: + psnd_lfilter, psnd_lfilter_spans (first- and second-order recursive filter sections as an exact scan parallel over time, both directions: psnd_lfilter.hip); 0.1.43: + psnd_istft_reim / _reim_mr / _reim_bwd (masked inverse STFT on (re, im), native in both directions); 0.1.42: + psnd_adam_step_sched (the learning rate of an in-flight step chosen on the device by the count of steps that succeeded: LR schedulers on the Trainer's device-skip path); 0.1.41: + psnd_stft_mr_* / psnd_istft_mr (mixed-radix STFT forward, backward, inverse for even n_fft = 2^a 3^b 5^c up to 4096: psnd_stft_mr.hip); 0.1.40: + psnd_ipreemph_fwd / _bwd, psnd_volnorm_fwd / _reverse (InversePreEmphasis as a scan parallel over time, VolNormConv per hop: psnd_sound.hip); 0.1.39: + psnd_groupnorm1_drop_fwd / _drop_bwd, psnd_rng_seed / psnd_rng_next (dropout formed inside the GroupNorm kernels, Philox4x32-10 mask, device-side {seed, call}); 0.1.38: + psnd_lstft_* (LearnableSTFT: strided-view analysis, polyphase synthesis, slab basis gradient); 0.1.37: psnd_groupnorm1_* take 2 C doubles of scratch per sample (one pair of sums per row: no atomics; round 6); 0.1.36: + psnd_linear1x1_fwd_ex, psnd_linear1x1_bwd_ex takes io_h (round 6: the hidden tensor of Conv1d -> ReLU -> Conv1d stored as bf16 under autocast); 0.1.35: + psnd_linear1x1_bwd_ex (round 6: the ReLU between two projections masks in the producing GEMM); 0.1.34: + psnd_im2col_f32 / psnd_col2im_f32 (round 6: the fp32 instance of the conv stack); 0.1.33: + psnd_cl_colsum, psnd_grad_pack_bf16 / _unpack_bf16 (round 5); 0.1.32: + psnd_mha_bwd_parts, psnd_convtr1d_cl_bwd takes either role alone (round 4); 0.1.31: psnd_mha_fwd / _bwd take `bf16` (round 3); 0.1.30: + psnd_polar_bwd, psnd_grad_sumsq
 
 extern "C" const char *psnd_last_error(void) { return g_err; }
 

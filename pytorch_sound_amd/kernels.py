@@ -2,7 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and streams; every number is produced
 by libpsnd_hip.so.  No function in this module has a CPU or eager fallback - a CPU tensor
-or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder`, the `griffinlim*` functions, `mel_inverse`, `loudness`, `level` and `apply_gain` alone also take CPU tensors: there the
+or a missing library raises.  (`lfilter`, `resample_poly`, `silence_ranges`, `yin_f0`, `phase_vocoder`, the `griffinlim*` functions, `mel_inverse`, `loudness`, `level`, `apply_gain`, `sep_metric` and `mix_at_snr` alone also take CPU tensors: there the
 scipy call or the numpy restatement IS the implementation or the definition; a HIP tensor never reaches it.)
 """
 import ctypes
@@ -1760,6 +1760,266 @@ def apply_gain(wav, gain, lengths=None, channels=None, out=None):
         with on(wav.device) as hip:
             hip.psnd_gain_rows(xf, N, C, T, lengths, gain, y)
     return out if out is not None else y.reshape(wav.shape).to(wav.dtype)
+
+
+# ---- separation metrics (include/psnd.h: SNR / SI-SDR / SD-SDR, permutation-invariant matching, mixing at an SNR) ---------------------------
+SEP_KINDS = ('snr', 'si_sdr', 'sd_sdr')                  # the `kind` of the C ABI is the index
+SEP_EPS = float(np.finfo(np.float32).eps)                # torchmetrics' choice
+
+
+def sep_span():
+    """psnd_sep_span: the samples of a row per workgroup of the moment launch, the one size the kernel's seams depend on"""
+    return int(lib().psnd_sep_span())
+
+
+def sep_max_sources():
+    """psnd_sep_max_sources: the most sources per item the permutation search takes"""
+    return int(lib().psnd_sep_max_sources())
+
+
+def _sep_config(kind, zero_mean, eps, who='sep_metric'):
+    if kind not in SEP_KINDS:
+        raise ValueError("%s: kind=%r - 'snr', 'si_sdr' or 'sd_sdr'" % (who, kind))
+    eps = SEP_EPS if eps is None else float(eps)
+    if not (math.isfinite(eps) and eps >= 0.0):
+        raise ValueError('%s: eps=%r - finite, at least 0' % (who, eps))
+    return SEP_KINDS.index(kind), int(bool(zero_mean)), eps
+
+
+def _sep_shape(est, target, who):
+    """(leading shape, B, S, T) of estimates and targets (..., S, T)"""
+    if tuple(est.shape) != tuple(target.shape) or len(est.shape) < 2:
+        raise _lib.PsndError('%s: estimates and targets (..., S, T) of one shape expected, got %s and %s'
+                             % (who, tuple(est.shape), tuple(target.shape)))
+    lead = tuple(est.shape[:-2])
+    S, T = int(est.shape[-2]), int(est.shape[-1])
+    if S < 1:
+        raise _lib.PsndError('%s: S=%d sources' % (who, S))
+    return lead, math.prod(lead), S, T
+
+
+def sep_pair_values(kind, ee, ss, es, eps):
+    """the pair value of include/psnd.h in float64 numpy from the (centred) moments, any broadcastable shapes: dB in float64"""
+    ee, ss, es = (np.asarray(v, dtype=np.float64) for v in (ee, ss, es))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if kind == 'snr':
+            return 10.0 * np.log10((ss + eps) / (np.maximum(ss - 2.0 * es + ee, 0.0) + eps))
+        a = (es + eps) / (ss + eps)
+        tg = a * a * ss
+        n = tg - 2.0 * a * es + ee if kind == 'si_sdr' else ss - 2.0 * es + ee
+        return 10.0 * np.log10((tg + eps) / (np.maximum(n, 0.0) + eps))
+
+
+def sep_best_perm(pv):
+    """the permutation p that maximises sum_i pv[i][p[i]] of a float32 pair matrix (S, S) - the values added in float64 in ascending i, the
+    permutations walked in lexicographic order, a later one winning only by a strictly larger sum - as a list"""
+    import itertools
+    S = pv.shape[0]
+    best, top = list(range(S)), None
+    for p in itertools.permutations(range(S)):
+        s = 0.0
+        for i in range(S):
+            s += float(pv[i, p[i]])
+        if top is None or s > top:
+            best, top = list(p), s
+    return best
+
+
+def sep_metric_host(est, target, kind, zero_mean=False, eps=None, lengths=None, pit=False, return_perm=False, return_pairs=False):
+    """the definition of include/psnd.h in float64 numpy on arrays (..., S, T): float32 values (..., S) in dB - estimate i against target
+    perm[i] - and on request the int32 permutation (..., S) and the float32 pair matrix (..., S, S).  The moments are taken of the explicitly
+    centred rows (zero_mean), so nothing is lost to a difference.  An item that holds a non-finite sample before its length reads NaN and the
+    identity permutation."""
+    _sep_config(kind, zero_mean, eps)
+    eps = SEP_EPS if eps is None else float(eps)
+    est, target = np.asarray(est), np.asarray(target)
+    lead, B, S, T = _sep_shape(est, target, 'sep_metric')
+    lens = _host_lengths(lengths, B, T, 'sep_metric')
+    E, G = est.reshape(B, S, T), target.reshape(B, S, T)
+    value = np.zeros((B, S), dtype=np.float32)
+    perm = np.tile(np.arange(S, dtype=np.int32), (B, 1))
+    pair = np.zeros((B, S, S), dtype=np.float32)
+    for b in range(B):
+        e, s = E[b, :, :lens[b]].astype(np.float64), G[b, :, :lens[b]].astype(np.float64)
+        if not (np.isfinite(e).all() and np.isfinite(s).all()):
+            value[b], pair[b] = np.nan, np.nan
+            continue
+        if zero_mean and lens[b] > 0:
+            e, s = e - e.mean(axis=-1, keepdims=True), s - s.mean(axis=-1, keepdims=True)
+        ee, ss, es = (e * e).sum(axis=-1), (s * s).sum(axis=-1), e @ s.T
+        pair[b] = sep_pair_values(kind, ee[:, None], ss[None, :], es, eps).astype(np.float32)
+        if pit:
+            perm[b] = sep_best_perm(pair[b])
+        value[b] = pair[b][np.arange(S), perm[b]]
+    out = (value.reshape(lead + (S,)),) + ((perm.reshape(lead + (S,)),) if return_perm else ()) \
+        + ((pair.reshape(lead + (S, S)),) if return_pairs else ())
+    return out if len(out) > 1 else out[0]
+
+
+def _sep_rows(x, B, S, T):
+    """a HIP tensor (..., S, T) as (B, S, T) float32 rows the kernels can walk where they lie: any 4-byte start, unit stride in time, rows T apart"""
+    xf = x.reshape(B, S, T)
+    if xf.dtype != torch.float32:
+        xf = xf.float()
+    if B * S * T > 0 and (xf.stride(2) != 1 or (S > 1 and xf.stride(1) != T) or (B > 1 and xf.stride(0) != S * T)):
+        xf = xf.contiguous()
+    return xf
+
+
+class _SepMetric(torch.autograd.Function):
+    """psnd_sep_metric_fwd / _bwd on (B, S, T) float32 rows: (loss or None, value, perm, pair or None, nan_flag or None).  Keeps `stats` and
+    `perm` for the backward; differentiable in the estimates and the targets through the loss and through the values."""
+
+    @staticmethod
+    def forward(ctx, est, target, lengths, kind, zero_mean, eps, pit, want_pair, want_loss):
+        B, S, T = est.shape
+        dev = est.device
+        value = torch.empty((B, S), dtype=torch.float32, device=dev)
+        perm = torch.empty((B, S), dtype=torch.int32, device=dev)
+        pair = torch.empty((B, S, S), dtype=torch.float32, device=dev) if want_pair else None
+        loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+        flag = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+        stats = torch.empty(int(lib().psnd_sep_stats_doubles(B, S)), dtype=torch.float64, device=dev)
+        scratch = torch.empty(int(lib().psnd_sep_scratch_bytes(B, S, T)) // 8, dtype=torch.float64, device=dev)
+        with on(dev) as hip:
+            hip.psnd_sep_metric_fwd(est, target, B, S, T, lengths, kind, zero_mean, eps, int(bool(pit)), scratch, stats, value, perm, pair,
+                                    loss, flag)
+        ctx.save_for_backward(est, target, stats, perm)
+        ctx.cfg = (kind, zero_mean, eps)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*[t for t in (perm, pair, flag) if t is not None])
+        return loss, value, perm, pair, flag
+
+    @staticmethod
+    def backward(ctx, g_loss, g_value, *_):
+        est, target, stats, perm = ctx.saved_tensors
+        if g_loss is None and g_value is None:
+            return (None,) * 9
+        B, S, T = est.shape
+        kind, zero_mean, eps = ctx.cfg
+        g_loss = None if g_loss is None else g_loss.to(torch.float32).contiguous()
+        g_value = None if g_value is None else g_value.to(torch.float32).contiguous()
+        g_est = torch.empty((B, S, T), dtype=torch.float32, device=est.device)
+        g_target = torch.empty((B, S, T), dtype=torch.float32, device=est.device) if ctx.needs_input_grad[1] else None
+        with on(est.device) as hip:
+            hip.psnd_sep_metric_bwd(est, target, B, S, T, kind, zero_mean, eps, stats, perm, g_loss, g_value, g_est, g_target)
+        return (g_est if ctx.needs_input_grad[0] else None, g_target) + (None,) * 7
+
+
+def sep_metric_loss(est, target, kind, zero_mean=False, eps=None, lengths=None, pit=False, return_pairs=False, want_loss=True):
+    """one call of psnd_sep_metric_fwd on HIP tensors (..., S, T): (loss, value, perm, pair, nan_flag) - the scalar -mean(value) and
+    isnan(loss) as float32 device scalars (None without want_loss), float32 values and int32 permutation (..., S), the pair matrix
+    (..., S, S) or None.  Differentiable in both inputs through `loss` and `value`; nothing is read back by the host."""
+    if not (isinstance(est, torch.Tensor) and isinstance(target, torch.Tensor) and est.is_cuda and target.is_cuda):
+        raise _lib.PsndError('sep_metric: HIP tensors are expected here (CPU tensors and numpy arrays take sep_metric_host)')
+    if not (est.is_floating_point() and target.is_floating_point()):
+        raise _lib.PsndError('sep_metric: floating inputs expected, got %s and %s' % (est.dtype, target.dtype))
+    k, zm, eps = _sep_config(kind, zero_mean, eps)
+    lead, B, S, T = _sep_shape(est, target, 'sep_metric')
+    if S > sep_max_sources():
+        raise _lib.PsndError('sep_metric: S=%d sources, the permutation search takes at most %d' % (S, sep_max_sources()))
+    lengths = _device_lengths(lengths, B, est.device, 'sep_metric')
+    if B * T == 0:                                       # nothing to launch: the formulas on zero moments; no sample, no gradient
+        host = sep_metric_host(np.zeros((B, S, T), np.float32), np.zeros((B, S, T), np.float32), kind, zero_mean, eps, None, pit, True, True)
+        value, perm, pair = (torch.from_numpy(v).to(est.device) for v in host)
+        loss = -value.mean() if B else torch.zeros((), device=est.device)
+        flag = torch.isnan(loss).float()
+    else:
+        e, t = _sep_rows(est, B, S, T), _sep_rows(target, B, S, T)
+        loss, value, perm, pair, flag = _SepMetric.apply(e, t, lengths, k, zm, eps, bool(pit), bool(return_pairs), bool(want_loss))
+    pair = pair.reshape(lead + (S, S)) if return_pairs else None
+    return (loss, value.reshape(lead + (S,)), perm.reshape(lead + (S,)), pair, flag) if want_loss else \
+        (None, value.reshape(lead + (S,)), perm.reshape(lead + (S,)), pair, None)
+
+
+def sep_metric(est, target, kind, zero_mean=False, eps=None, lengths=None, pit=False, return_perm=False, return_pairs=False):
+    """SNR ('snr'), scale-invariant SDR ('si_sdr') or scale-dependent SDR ('sd_sdr') in dB of S estimates against S targets per item, the
+    definition of include/psnd.h: `est`, `target` (..., S, T) -> float32 values (..., S).  `zero_mean`: take the means out first; `eps`: the
+    regulariser (default float32 machine epsilon); `lengths`: per-ITEM valid lengths (leading shape), clamped to [0, T]; `pit`: match the
+    estimates with the targets by the permutation that maximises the sum of the values (estimate i with target perm[i], ties to the
+    lexicographically first).  return_perm / return_pairs: also the int32 permutation (..., S) / the whole float32 pair matrix
+    (..., S, S), in that order.  An item that holds a non-finite sample reads NaN and the identity permutation.
+
+    HIP tensors run psnd_separation.hip - at most three launches forward (without the loss: two), one backward, no host synchronisation -
+    and carry a gradient to the estimates and the targets; numpy arrays and CPU tensors go through `sep_metric_host` in float64, without
+    a gradient."""
+    if isinstance(est, torch.Tensor) and est.is_cuda:
+        _, value, perm, pair, _ = sep_metric_loss(est, target, kind, zero_mean, eps, lengths, pit, return_pairs, want_loss=False)
+        out = (value,) + ((perm,) if return_perm else ()) + ((pair,) if return_pairs else ())
+        return out if len(out) > 1 else out[0]
+    tensor = isinstance(est, torch.Tensor)
+    to_np = lambda v: v.detach().to(torch.float64 if v.dtype == torch.bfloat16 else v.dtype).cpu().numpy() if isinstance(v, torch.Tensor) else v  # noqa: E731
+    r = sep_metric_host(to_np(est), to_np(target), kind, zero_mean, eps, lengths, pit, return_perm, return_pairs)
+    if not tensor:
+        return r
+    return tuple(torch.from_numpy(np.array(v)) for v in r) if isinstance(r, tuple) else torch.from_numpy(np.array(r))
+
+
+def mix_at_snr_host(x, z, snr, lengths=None):
+    """torchaudio's add_noise by the definition of include/psnd.h in numpy: x + g z before a row's length with g = sqrt(sum x^2 / sum z^2)
+    10^(-snr / 20) in float64, rounded to float32, x behind it; g = 0 for a silent or non-finite row.  (float32 result, the float32 gains)"""
+    x, z = np.asarray(x), np.asarray(z)
+    if x.shape != z.shape or x.ndim < 1:
+        raise _lib.PsndError('mix_at_snr: signal and noise (..., T) of one shape expected, got %s and %s' % (x.shape, z.shape))
+    T = int(x.shape[-1])
+    R = math.prod(x.shape[:-1])
+    lens = _host_lengths(lengths, R, T, 'mix_at_snr')
+    snr = np.asarray(snr, dtype=np.float32).reshape(-1)
+    if snr.size not in (1, R):
+        raise _lib.PsndError('mix_at_snr: %d SNRs for %d rows' % (snr.size, R))
+    xf, zf = x.reshape(R, T).astype(np.float32), z.reshape(R, T).astype(np.float32)
+    y, gain = xf.copy(), np.zeros(R, dtype=np.float32)
+    for r in range(R):
+        a, b = xf[r, :lens[r]].astype(np.float64), zf[r, :lens[r]].astype(np.float64)
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            continue
+        xx, zz = float((a * a).sum()), float((b * b).sum())
+        if xx > 0.0 and zz > 0.0:
+            with np.errstate(over='ignore'):
+                gain[r] = np.float32(math.sqrt(xx / zz) * np.power(10.0, -np.float64(snr[r if snr.size > 1 else 0]) / 20.0))
+            y[r, :lens[r]] = (a + np.float64(gain[r]) * b).astype(np.float32)
+    return y.reshape(x.shape), gain.reshape(x.shape[:-1])
+
+
+def mix_at_snr(x, z, snr, lengths=None, out=None, return_gain=False):
+    """`x` with the noise `z` added at `snr` dB (torchaudio's add_noise, include/psnd.h): x + g z before a row's length, x behind it, with
+    g = sqrt(sum x^2 / sum z^2) 10^(-snr / 20) per row of (..., T); `snr`: one number or one per row (a tensor stays on its device).  A row
+    that is silent in either input or holds a non-finite sample comes back unchanged (g = 0).  On HIP tensors psnd_snr_gain and
+    psnd_mix_rows: three launches, the gain never leaves the device, capturable; `out`: a contiguous float32 HIP tensor of x's shape, `x`
+    itself for in place.  numpy arrays and CPU tensors go through `mix_at_snr_host`.  No gradient."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        if out is not None:
+            raise _lib.PsndError('mix_at_snr: out= is for HIP tensors')
+        tensor = isinstance(x, torch.Tensor)
+        to_np = lambda v: v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else v  # noqa: E731
+        y, g = mix_at_snr_host(to_np(x), to_np(z), to_np(snr), lengths)
+        if tensor:
+            y, g = torch.from_numpy(y).to(x.dtype), torch.from_numpy(np.array(g))
+        return (y, g) if return_gain else y
+    if not (isinstance(z, torch.Tensor) and z.is_cuda) or x.shape != z.shape:
+        raise _lib.PsndError('mix_at_snr: signal and noise of one shape on one device expected')
+    xf, lead, R, _, T = _meter_rows(x, None, 'mix_at_snr')
+    zf = _meter_rows(z, None, 'mix_at_snr')[0]
+    dev = x.device
+    snr = torch.as_tensor(snr, dtype=torch.float32).reshape(-1)
+    if snr.numel() not in (1, R):
+        raise _lib.PsndError('mix_at_snr: %d SNRs for %d rows' % (snr.numel(), R))
+    snr = snr.to(dev).contiguous()
+    lengths = _device_lengths(lengths, R, dev, 'mix_at_snr')
+    if out is None:
+        y = torch.empty((R, T), dtype=torch.float32, device=dev)
+    else:
+        if out.dtype != torch.float32 or out.shape != x.shape or not out.is_cuda or not out.is_contiguous():
+            raise _lib.PsndError('mix_at_snr: out must be a contiguous float32 HIP tensor of the shape %s' % (tuple(x.shape),))
+        y = out
+    gain = torch.zeros(R, dtype=torch.float32, device=dev)
+    if R * T > 0:
+        scratch = torch.empty(int(lib().psnd_sep_scratch_bytes(R, 1, T)) // 8, dtype=torch.float64, device=dev)
+        with on(dev) as hip:
+            hip.psnd_snr_gain(xf, zf, R, T, lengths, snr, snr.numel(), scratch, gain)
+            hip.psnd_mix_rows(xf, zf, R, T, lengths, gain, y)
+    y = out if out is not None else y.reshape(x.shape).to(x.dtype)
+    return (y, gain.reshape(lead)) if return_gain else y
 
 
 def _count(name, v, least):

@@ -247,6 +247,42 @@ class LoudnessNorm(torch.nn.Module):
         return 'sr=%r, target_level=%r, kind=%r' % (self.sr, self.target_level, self.kind)
 
 
+class SeparationLoss(torch.nn.Module):
+    """The waveform-domain objective of a separator as one autograd node, no parameters: ``-mean`` over items and sources of the SNR
+    ('snr'), scale-invariant SDR ('si_sdr') or scale-dependent SDR ('sd_sdr') in dB of the estimates (B, S, T) - or (B, T), one source -
+    against the targets, by the definition of include/psnd.h.  ``pit``: permutation-invariant training, every item's estimates matched
+    with its targets by the permutation that maximises the sum of the values; the choice is made on the device, so the step stays
+    capturable (``Trainer.graph_steps``).  ``zero_mean`` defaults to True for 'si_sdr' and False otherwise, ``eps`` to float32 machine
+    epsilon (torchmetrics' choices); ``lengths``: per-item valid lengths, the gradient is exactly 0 behind them.
+
+    On HIP tensors only (psnd_separation.hip: three launches forward, one backward; on the host compose the loss from ``utils.metrics``).
+    The returned scalar carries ``loss.psnd_nan_flag``, formed by the launch that forms the loss, which ``Trainer`` takes instead of a
+    launch of its own; after a forward ``last_perm`` holds the int32 device permutation (B, S) and ``last_value`` the detached values."""
+
+    def __init__(self, kind: str = 'si_sdr', pit: bool = False, zero_mean=None, eps=None):
+        super().__init__()
+        self.zero_mean = (kind == 'si_sdr') if zero_mean is None else bool(zero_mean)
+        K._sep_config(kind, self.zero_mean, eps, 'SeparationLoss')
+        self.kind, self.pit, self.eps = kind, bool(pit), eps
+        self.last_perm = self.last_value = None
+
+    def forward(self, est: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
+        if est.dim() not in (2, 3) or est.shape != target.shape:
+            raise RuntimeError('SeparationLoss expects estimates and targets (B, S, T) or (B, T) of one shape, got %s and %s'
+                               % (tuple(est.shape), tuple(target.shape)))
+        if not est.is_cuda:
+            raise RuntimeError('SeparationLoss is the HIP formulation; on the host compose the loss from utils.metrics')
+        if est.dim() == 2:
+            est, target = est.unsqueeze(1), target.unsqueeze(1)
+        loss, value, perm, _, flag = K.sep_metric_loss(est, target, self.kind, self.zero_mean, self.eps, lengths, self.pit)
+        loss.psnd_nan_flag = flag                          # isnan(loss), written by the launch that formed the loss (Trainer._nan_flag)
+        self.last_perm, self.last_value = perm, value.detach()
+        return loss
+
+    def extra_repr(self) -> str:
+        return 'kind=%r, pit=%r, zero_mean=%r, eps=%r' % (self.kind, self.pit, self.zero_mean, self.eps)
+
+
 class GriffinLim(torch.nn.Module):
     """``kernels.griffinlim`` as a module on magnitudes (N, K, F) or (K, F) with K = n_fft // 2 + 1, no parameters: ``n_iter`` iterations
     of fast Griffin-Lim (torchaudio's / librosa's definition, include/psnd.h), (F - 1) hop_length samples per item.  ``power``: the

@@ -10,6 +10,8 @@
     mel_to_magnitude, mel_to_wave  a linear magnitude, and a waveform, from a mel spectrogram alone (the reference has none)
     loudness, normalize            integrated loudness in LUFS and level normalisation (the reference runs every file through
                                    ffmpeg-normalize on the host: scripts/preprocess.py:32-41)
+    add_noise                      a signal with noise mixed in at a wanted SNR (torchaudio's add_noise; the reference's
+                                   make_background_numpy only cuts the noise beds: scripts/preprocess.py)
 
 A numpy array goes through scipy on the host, exactly as in the reference.  A torch tensor comes back as a tensor of the same dtype and
 device through `kernels.lfilter`: on a HIP tensor the native scan of psnd_lfilter.hip in both directions (differentiable in the signal,
@@ -330,6 +332,20 @@ def normalize(wav, sr, target_level=-23.0, kind='ebu', lengths=None, channels=No
     level = kernels.loudness_host(x, sr, lengths, channels) if kind == 'ebu' else kernels.level_host(x, kind, lengths, channels)
     y = kernels.apply_gain_host(x, kernels.gain_of_level(level, target), lengths, channels)
     return torch.from_numpy(y).to(wav.dtype) if _is_tensor(wav) else y
+
+
+def add_noise(wav, noise, snr, lengths=None):
+    """`wav` with `noise` mixed in at `snr` dB per row of (..., T), torchaudio's `add_noise` by the definition of include/psnd.h:
+    wav + g noise before a row's length and wav behind it, g = sqrt(sum wav^2 / sum noise^2) 10^(-snr / 20) from float64 sums.  `snr`: one
+    number or one per row.  A row that is silent in either input, or holds a non-finite sample, comes back unchanged.  numpy in ->
+    float32 numpy out; tensor in -> tensor of the same dtype and device out; on HIP tensors `kernels.mix_at_snr` (psnd_separation.hip),
+    the gain never leaves the device and the call can be captured.  Not differentiable: an input that requires grad raises."""
+    for v in (wav, noise, snr):
+        if _is_tensor(v) and v.requires_grad:
+            raise kernels.PsndError('add_noise is not differentiable: detach the inputs')
+    if _is_tensor(wav) != _is_tensor(noise):
+        raise kernels.PsndError('add_noise: signal and noise must both be tensors or both be arrays')
+    return kernels.mix_at_snr(wav, noise, snr, lengths)
 
 
 def get_wav_duration(file):
